@@ -5,14 +5,20 @@ One "step" = one steady-state frame of the reference loop (train.py:119-131): fo
 histogram equalisation + RAFT(12 iterations) + fused backward warp, LossFunction, hand-written backward, one
 flat-bucket gradient all-reduce over RCCL (N > 1), clip_grad_norm_(5) + Adam.  Frames are synthetic
 (zero-tig_amd/synth.py) and already resident in HBM when the timed region starts (`value`); the same K steps are timed
-a second time with the reference's per-step host->device copy of the frame (train.py:125) inside the step (`with_h2d`).
+a second time with the reference's per-step host->device copy of the frame (train.py:125) inside the step (`with_h2d`, --full).
 
 Launch: `python bench.py --gpus N ...` starts N ranks itself (one process per GPU, RCCL) when it is not already running
 under torch.distributed.run / torchrun (WORLD_SIZE unset); under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (dominant kernel), `roofline_extra` (the warp and
-the correlation volume, BASELINE.json's HBM targets) -- all timed live with HIP events on the launch stream in a separate
-pass after the timed region -- and `cpu_baseline` (the CPU oracle timed on this box's host cores, rank 0, N == 1 only).
+Prints ONE JSON line (rank 0) with the driver's contract.  A plain run sets up, warms up, times the K steps and prints it;
+everything else is measured only with --full: `with_h2d`, `roofline` (dominant kernel), `roofline_extra` (the warp and the
+correlation volume, BASELINE.json's HBM targets) -- all timed live with HIP events on the launch stream in separate passes
+after the timed region -- and `cpu_baseline` (the CPU oracle timed on the host cores, rank 0, N == 1 only).  Without --full
+those keys are null.
+
+--dump-outputs DIR writes what the last timed step handed back (loss, gradient norm, updated parameters and gradients,
+BatchNorm running statistics, the enhanced frame and its recurrent partner) as DIR/<name>.npy (rank 0), so that two builds
+can be compared output for output: the inputs depend only on the arguments.
 """
 import argparse
 import importlib
@@ -26,9 +32,10 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-PEAK_F32_MFMA_TFLOPS = 157.3          # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32, dense
+PEAK_F32_MFMA_TFLOPS = 157.3          # MI355X: v_mfma_f32_16x16x4_f32, dense
 PEAK_BF16_MFMA_TFLOPS = 2500.0
 PEAK_HBM_GBS = 8000.0
+DUMP_MAX_ELEMS = 7_500_000             # per dumped array (float32): a larger one is written as a fixed, seeded sample (64 MB cap in all)
 
 
 def parse():
@@ -40,16 +47,37 @@ def parse():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--of_scale", type=int, default=3)
     ap.add_argument("--dataset", type=str, default="RLV")
-    ap.add_argument("--cpu-baseline", type=str, default="1080p", choices=["540p", "1080p", "none"])
+    ap.add_argument("--cpu-baseline", type=str, default="1080p", choices=["540p", "1080p", "none"], help="--full only")
     ap.add_argument("--frames", type=int, default=6, help="distinct synthetic frames kept in HBM (cycled)")
     ap.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32"],
                     help="bf16: activations+weights bf16 in HBM, fp32 accumulate (BASELINE config 3); fp32: exact-fp32 parity mode")
     ap.add_argument("--graph", type=int, default=1, help="1: replay the step from a captured hipGraph (default); 0: eager launches")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the steps with the per-step H2D frame copy, the live roofline pass and the CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     return ap.parse_args()
 
 
 def log(msg):
     print("[bench] " + msg, file=sys.stderr, flush=True)
+
+
+def dump_outputs(arrays, out_dir):
+    """{name: array} -> out_dir/<name>.npy as float32.  An array of more than DUMP_MAX_ELEMS elements is written as a fixed sample
+    (sorted indices of a seeded generator over the flattened array), so the same arguments always pick the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(20240607).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64_000_000, total
+    return total
 
 
 def host_cores():
@@ -170,17 +198,18 @@ def main():
     H, W = a.height, a.width
     nfr = max(2, min(a.frames, a.steps + a.warmup + 1))
     # each rank owns its own clip (seed 2 + 1000*rank): frame-level data parallelism with per-rank recurrent cache
-    # host side of `with_h2d`: what the loader hands over in device-ingest mode -- the DECODED frame, uint8 [1,H,W,3] (the synthetic
-    # frames are quantised to k/255 like an 8-bit PNG, so the device's ToTensor reproduces the float frame bit for bit: checked)
+    # host side of `with_h2d` (--full): what the loader hands over in device-ingest mode -- the DECODED frame, uint8 [1,H,W,3] (the
+    # synthetic frames are quantised to k/255 like an 8-bit PNG, so the device's ToTensor reproduces the float frame bit for bit: checked)
     net._plan()
     host_frames, frames = [], []
     for t in range(nfr):
         f32 = torch.from_numpy(synth.lowlight_frame(t, H, W, seed=2 + 1000 * rank))
-        u8 = torch.round(f32[0].permute(1, 2, 0) * 255.0).to(torch.uint8).contiguous()[None].pin_memory()
-        host_frames.append(u8)
         frames.append(f32.to(dev))
-        if t == 0:
-            assert torch.equal(net._ops.ingest_u8(u8.to(dev), size=(W, H)), frames[0]), "device ToTensor must reproduce the float frame"
+        if a.full:
+            u8 = torch.round(f32[0].permute(1, 2, 0) * 255.0).to(torch.uint8).contiguous()[None].pin_memory()
+            host_frames.append(u8)
+            if t == 0:
+                assert torch.equal(net._ops.ingest_u8(u8.to(dev), size=(W, H)), frames[0]), "device ToTensor must reproduce the float frame"
         if rank == 0:
             log("synthetic frame %d/%d resident in HBM" % (t + 1, nfr))
 
@@ -232,99 +261,109 @@ def main():
     dt, med_ms, last_loss = timed(False)
     if rank == 0:
         log("timed region done: %.2f ms/step (median of the per-step HIP-event times %.2f ms)" % (1e3 * dt / a.steps, med_ms))
-    dt_h, med_h, _ = timed(True)
-    if rank == 0:
-        log("with the per-step H2D copy of the frame: %.2f ms/step" % (1e3 * dt_h / a.steps))
     value = world * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        # what a caller of the step holds after the last timed step (taken before --full's passes step the model further)
+        bn = net.enhance.conv[1]
+        nbytes = dump_outputs({"loss": np.array([last_loss]), "grad_norm": opt.gnorm.cpu().numpy(), "params": opt.fp.flat.cpu().numpy(),
+                               "grads": opt.fp.grad.cpu().numpy(), "bn_running_mean": bn.running_mean.cpu().numpy(),
+                               "bn_running_var": bn.running_var.cpu().numpy(), "enhanced_H3": net.last_H3.cpu().numpy(),
+                               "last_s3": net.last_s3.cpu().numpy()}, a.dump_outputs)
+        log("outputs of the last timed step written to %s (%.1f MB)" % (a.dump_outputs, nbytes / 1e6))
 
-    # ---- live roofline instrumentation, separate untimed pass (eager launches, HIP events around the matched kernels)
-    px = float(H) * W
-    h8, w8 = ((H // a.of_scale + 7) // 8), ((W // a.of_scale + 7) // 8)
-    npx = h8 * w8
-    prof = {"match": {(3, 3, 1, 64, 64, H, W): "conv64", (1, 1, 1, 256, npx, h8, w8): "corr", ("wgrad", 3, 64, 64, H, W): "wgrad64"}, "events": {}}
-    net._ops.profile = prof
-    eager = optim.TrainStep(net, opt, use_graph=False)
-    for _ in range(3):
-        eager(frames[it % nfr], is_new_seq=False)
-        it += 1
-    torch.cuda.synchronize()
-    net._ops.profile = None
+    dt_h = med_h = roof = extra = cpu = None
+    if a.full:
+        dt_h, med_h, _ = timed(True)
+        if rank == 0:
+            log("with the per-step H2D copy of the frame: %.2f ms/step" % (1e3 * dt_h / a.steps))
 
-    def avg_ms(name):
-        """mean of the per-launch HIP-event times of one kernel family (an event pair around a short kernel also times the pair
-        itself: `event_pair_overhead_ms` is reported next to the sub-50-us kernels; rocprofv3's averages are in profiles/)"""
-        ev = prof["events"].get(name, [])
-        return (sum(s.elapsed_time(e) for s, e in ev) / len(ev), len(ev)) if ev else (None, 0)
+        # ---- live roofline instrumentation, separate untimed pass (eager launches, HIP events around the matched kernels)
+        px = float(H) * W
+        h8, w8 = ((H // a.of_scale + 7) // 8), ((W // a.of_scale + 7) // 8)
+        npx = h8 * w8
+        prof = {"match": {(3, 3, 1, 64, 64, H, W): "conv64", (1, 1, 1, 256, npx, h8, w8): "corr", ("wgrad", 3, 64, 64, H, W): "wgrad64"}, "events": {}}
+        net._ops.profile = prof
+        eager = optim.TrainStep(net, opt, use_graph=False)
+        for _ in range(3):
+            eager(frames[it % nfr], is_new_seq=False)
+            it += 1
+        torch.cuda.synchronize()
+        net._ops.profile = None
 
-    # an empty HIP-event pair on the launch stream: what the bracket itself adds to a short kernel's reading
-    pairs = []
-    for _ in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        e1.record()
-        pairs.append((e0, e1))
-    torch.cuda.synchronize()
-    ev_overhead_ms = sorted(a.elapsed_time(b) for a, b in pairs)[len(pairs) // 2]
+        def avg_ms(name):
+            """mean of the per-launch HIP-event times of one kernel family (an event pair around a short kernel also times the pair
+            itself: `event_pair_overhead_ms` is reported next to the sub-50-us kernels; rocprofv3's averages are in profiles/)"""
+            ev = prof["events"].get(name, [])
+            return (sum(s.elapsed_time(e) for s, e in ev) / len(ev), len(ev)) if ev else (None, 0)
 
-    roof, extra = None, {}
-    ms, nl = avg_ms("conv64")
-    if ms is not None:
-        flops = 2.0 * 9 * 64 * 64 * px
-        tf = flops / (ms * 1e-3) / 1e12
-        if a.precision == "bf16":
-            # bf16: 288 FLOP/B sits at the ridge (2500 TF / 8 TB/s = 312); priced against HBM.  Per launch the kernel reads the
-            # 64-ch bf16 input once and writes the 64-ch output once (the three dgrad launches also read the residual df).
-            # With the BatchNorm-backward sums fused in (zero-tig_amd/engine.py: default at this size), two of the three dgrad
-            # launches also read the previous block's pre-activation z once -- the read of the separate statistics pass they replace.
-            fused_bn = os.environ.get("ZT_FUSED_BN_BWD", "1") == "1" and \
-                ((W + 31) // 32) * ((H + 7) // 8) >= int(os.environ.get("ZT_STATS_FUSE_MIN_TILES", "1024"))
-            alg = (3 * (2 * px * 64 * 2) + 3 * (3 * px * 64 * 2) + (2 * px * 64 * 2 if fused_bn else 0)) / 6.0
-            gbs = alg / (ms * 1e-3) / 1e9
-            roof = {"bound": "hbm", "kernel": "conv_rs_bf16_kernel<2,2,true,2,0,*> (Enhancer 64->64 3x3: 3 fwd + 3 dgrad launches per step)",
-                    "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS, "traffic": None,
-                    "launches": nl, "avg_ms": ms, "algorithmic_bytes_per_launch": alg, "bn_backward_sums_fused": fused_bn,
-                    "mfma_view": {"achieved_TFLOPs": tf, "peak_TFLOPs": PEAK_BF16_MFMA_TFLOPS, "frac": tf / PEAK_BF16_MFMA_TFLOPS,
-                                  "algorithmic_flops_per_launch": flops}}
-            try:        # NOT measured in this run: HBM traffic of the same kernels from the committed PMC passes (profiles/)
-                src = "profiles/r03_pmc_summary.json"
-                pm = json.load(open(os.path.join(ROOT, src)))["kernels"]
-                ks = [v for k, v in pm.items() if k.startswith("conv_rs_bf16_kernel<2, 2, true, 2, 0,")]
-                if (H, W) == (1080, 1920) and ks:
-                    nd = sum(v["dispatches"] for v in ks)
-                    roof["traffic_from_profile"] = {"bytes_per_launch": sum(v["hbm_bytes_per_launch_avg"] * v["dispatches"] for v in ks) / nd,
-                                                    "source": src}
-            except Exception:
-                pass
-        else:
-            roof = {"bound": "mfma", "kernel": "conv_mfma_f32_kernel<3,3,1,4> (Enhancer 64->64 3x3, fwd+dgrad)", "achieved": tf,
-                    "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": tf / PEAK_F32_MFMA_TFLOPS, "traffic": None,
-                    "launches": nl, "avg_ms": ms, "algorithmic_flops_per_launch": flops}
-    ms, nl = avg_ms("warp2")
-    if ms is not None:          # utils.py:203-230 x2 fused: read 2 images + flow, write 2 images (fp32 planar)
-        alg = 4 * px * 3 * 4 + (H // a.of_scale) * (W // a.of_scale) * 2 * 4.0
-        extra["warp2_kernel"] = {"bound": "hbm", "achieved": alg / (ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                 "frac": alg / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "avg_ms": ms, "launches": nl,
-                                 "algorithmic_bytes_per_launch": alg, "event_pair_overhead_ms": ev_overhead_ms}
-    ms, nl = avg_ms("wgrad64")
-    if ms is not None:          # autograd of model.py:60-67's conv: reads the 64-ch input and the 64-ch output gradient once
-        alg = 2 * px * 64 * 2
-        extra["wgrad64_dma_bf16_kernel"] = {"bound": "hbm", "achieved": alg / (ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                            "frac": alg / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "avg_ms": ms, "launches": nl,
-                                            "algorithmic_bytes_per_launch": alg,
-                                            "mfma_frac": 2.0 * 9 * 64 * 64 * px / (ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS}
-    ms, nl = avg_ms("corr")
-    if ms is not None:          # corr.py:13-27, 52-60: the fp32 all-pairs volume and (bf16 mode: same launch) its 3 pooled levels written once, both feature maps read
-        fc = os.environ.get("ZT_FUSED_CORR", "auto")
-        fused = a.precision == "bf16" and (fc == "1" or (fc == "auto" and npx >= 8000))     # zero-tig_amd/raft.py: one launch for volume + pyramid
-        pyr = sum((h8 >> l) * (w8 >> l) for l in (1, 2, 3)) * float(npx) * 4 if fused else 0.0
-        alg = float(npx) * npx * 4 + pyr + 2 * npx * 256 * (2 if a.precision == "bf16" else 4)
-        extra["corr_volume"] = {"bound": "hbm", "achieved": alg / (ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                "frac": alg / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "avg_ms": ms, "launches": nl,
-                                "algorithmic_bytes_per_launch": alg, "event_pair_overhead_ms": ev_overhead_ms}
+        # an empty HIP-event pair on the launch stream: what the bracket itself adds to a short kernel's reading
+        pairs = []
+        for _ in range(20):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            e1.record()
+            pairs.append((e0, e1))
+        torch.cuda.synchronize()
+        ev_overhead_ms = sorted(a.elapsed_time(b) for a, b in pairs)[len(pairs) // 2]
 
-    cpu = None
-    if rank == 0 and world == 1 and a.cpu_baseline != "none":
-        cpu = cpu_baseline(a.cpu_baseline, a.of_scale, a.dataset)
+        roof, extra = None, {}
+        ms, nl = avg_ms("conv64")
+        if ms is not None:
+            flops = 2.0 * 9 * 64 * 64 * px
+            tf = flops / (ms * 1e-3) / 1e12
+            if a.precision == "bf16":
+                # bf16: 288 FLOP/B sits at the ridge (2500 TF / 8 TB/s = 312); priced against HBM.  Per launch the kernel reads the
+                # 64-ch bf16 input once and writes the 64-ch output once (the three dgrad launches also read the residual df).
+                # With the BatchNorm-backward sums fused in (zero-tig_amd/engine.py: default at this size), two of the three dgrad
+                # launches also read the previous block's pre-activation z once -- the read of the separate statistics pass they replace.
+                fused_bn = os.environ.get("ZT_FUSED_BN_BWD", "1") == "1" and \
+                    ((W + 31) // 32) * ((H + 7) // 8) >= int(os.environ.get("ZT_STATS_FUSE_MIN_TILES", "1024"))
+                alg = (3 * (2 * px * 64 * 2) + 3 * (3 * px * 64 * 2) + (2 * px * 64 * 2 if fused_bn else 0)) / 6.0
+                gbs = alg / (ms * 1e-3) / 1e9
+                roof = {"bound": "hbm", "kernel": "conv_rs_bf16_kernel<2,2,true,2,0,*> (Enhancer 64->64 3x3: 3 fwd + 3 dgrad launches per step)",
+                        "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS, "traffic": None,
+                        "launches": nl, "avg_ms": ms, "algorithmic_bytes_per_launch": alg, "bn_backward_sums_fused": fused_bn,
+                        "mfma_view": {"achieved_TFLOPs": tf, "peak_TFLOPs": PEAK_BF16_MFMA_TFLOPS, "frac": tf / PEAK_BF16_MFMA_TFLOPS,
+                                      "algorithmic_flops_per_launch": flops}}
+                try:        # NOT measured in this run: HBM traffic of the same kernels from the committed PMC passes (profiles/)
+                    src = "profiles/r03_pmc_summary.json"
+                    pm = json.load(open(os.path.join(ROOT, src)))["kernels"]
+                    ks = [v for k, v in pm.items() if k.startswith("conv_rs_bf16_kernel<2, 2, true, 2, 0,")]
+                    if (H, W) == (1080, 1920) and ks:
+                        nd = sum(v["dispatches"] for v in ks)
+                        roof["traffic_from_profile"] = {"bytes_per_launch": sum(v["hbm_bytes_per_launch_avg"] * v["dispatches"] for v in ks) / nd,
+                                                        "source": src}
+                except Exception:
+                    pass
+            else:
+                roof = {"bound": "mfma", "kernel": "conv_mfma_f32_kernel<3,3,1,4> (Enhancer 64->64 3x3, fwd+dgrad)", "achieved": tf,
+                        "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": tf / PEAK_F32_MFMA_TFLOPS, "traffic": None,
+                        "launches": nl, "avg_ms": ms, "algorithmic_flops_per_launch": flops}
+        ms, nl = avg_ms("warp2")
+        if ms is not None:          # utils.py:203-230 x2 fused: read 2 images + flow, write 2 images (fp32 planar)
+            alg = 4 * px * 3 * 4 + (H // a.of_scale) * (W // a.of_scale) * 2 * 4.0
+            extra["warp2_kernel"] = {"bound": "hbm", "achieved": alg / (ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                     "frac": alg / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "avg_ms": ms, "launches": nl,
+                                     "algorithmic_bytes_per_launch": alg, "event_pair_overhead_ms": ev_overhead_ms}
+        ms, nl = avg_ms("wgrad64")
+        if ms is not None:          # autograd of model.py:60-67's conv: reads the 64-ch input and the 64-ch output gradient once
+            alg = 2 * px * 64 * 2
+            extra["wgrad64_dma_bf16_kernel"] = {"bound": "hbm", "achieved": alg / (ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                                "frac": alg / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "avg_ms": ms, "launches": nl,
+                                                "algorithmic_bytes_per_launch": alg,
+                                                "mfma_frac": 2.0 * 9 * 64 * 64 * px / (ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS}
+        ms, nl = avg_ms("corr")
+        if ms is not None:          # corr.py:13-27, 52-60: the fp32 all-pairs volume and (bf16 mode: same launch) its 3 pooled levels written once, both feature maps read
+            fc = os.environ.get("ZT_FUSED_CORR", "auto")
+            fused = a.precision == "bf16" and (fc == "1" or (fc == "auto" and npx >= 8000))     # zero-tig_amd/raft.py: one launch for volume + pyramid
+            pyr = sum((h8 >> l) * (w8 >> l) for l in (1, 2, 3)) * float(npx) * 4 if fused else 0.0
+            alg = float(npx) * npx * 4 + pyr + 2 * npx * 256 * (2 if a.precision == "bf16" else 4)
+            extra["corr_volume"] = {"bound": "hbm", "achieved": alg / (ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                    "frac": alg / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, "avg_ms": ms, "launches": nl,
+                                    "algorithmic_bytes_per_launch": alg, "event_pair_overhead_ms": ev_overhead_ms}
+
+        if rank == 0 and world == 1 and a.cpu_baseline != "none":
+            cpu = cpu_baseline(a.cpu_baseline, a.of_scale, a.dataset)
 
     if rank == 0:
         label = "1080p" if (H, W) == (1080, 1920) else "%dx%d" % (H, W)
@@ -338,7 +377,9 @@ def main():
                           "global_batch": world, "launch": "hipGraph replay" if a.graph else "eager",
                           "collective": ("flat 370 KB gradient bucket all-reduced through torch.distributed backend '%s' (RCCL) every step, world=%d"
                                          % (dist.get_backend(), world)) if use_dist else "none (single process, no launcher)"},
-               "with_h2d": {"value": world * a.steps / dt_h, "ms_per_step": 1e3 * dt_h / a.steps, "ms_per_step_median": med_h,
+               "full": a.full,
+               "with_h2d": None if dt_h is None else
+                           {"value": world * a.steps / dt_h, "ms_per_step": 1e3 * dt_h / a.steps, "ms_per_step_median": med_h,
                             "note": "same K steps with every frame coming from pinned host memory as the loaders deliver it in device-ingest mode "
                                     "(decoded uint8 HWC, 6.2 MB at 1080p; the reference moves 24.9 MB of fp32, train.py:125): the next frame's copy is "
                                     "issued on a copy stream while the current step runs (optim.FramePrefetcher, as train.py does) and ToTensor "

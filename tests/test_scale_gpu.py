@@ -490,10 +490,11 @@ def test_scripts_train_resume_predict_pipeline(tmp_path, synth):
     assert len(list((tmp_path / "pred").rglob("*_denoise.png"))) == 4 and len(list((tmp_path / "pred").rglob("*_enhance.png"))) == 4
 
 
-def test_bench_one_rank_through_rccl():
+def test_bench_one_rank_through_rccl(tmp_path):
     """Multi-GPU readiness on the one-GPU box: bench.py started the way torch.distributed.run starts a rank (RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in the environment) with ONE rank: init_process_group("nccl"), the barriers of the timed region and the
-    flat-bucket all-reduce of optim.ClipAdam.step all go through RCCL (the same calls the N-rank job makes)."""
+    flat-bucket all-reduce of optim.ClipAdam.step all go through RCCL (the same calls the N-rank job makes).  --full adds the
+    roofline pass; --dump-outputs writes the last timed step's outputs."""
     import json
     import os
     import subprocess
@@ -502,11 +503,17 @@ def test_bench_one_rank_through_rccl():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", LOCAL_WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29600 + os.getpid() % 300), HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--height", "540",
-                        "--width", "960", "--cpu-baseline", "none"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                        "--width", "960", "--cpu-baseline", "none", "--full", "--dump-outputs", str(tmp_path / "out")],
+                       cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and "nccl" in line["config"]["collective"], line["config"]
     assert line["roofline"] is not None and np.isfinite(line["final_loss"])
+    assert line["with_h2d"]["ms_per_step"] > 0 and line["ms_per_step"] > 0
+    loss = np.load(str(tmp_path / "out" / "loss.npy"))
+    assert loss.dtype == np.float32 and float(loss[0]) == np.float32(line["final_loss"])
+    h3 = np.load(str(tmp_path / "out" / "enhanced_H3.npy"))
+    assert h3.shape == (1, 3, 540, 960) and np.isfinite(h3).all()
 
 
 def test_train_one_epoch_did_sdsd_underwater_layouts(tmp_path, synth):

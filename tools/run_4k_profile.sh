@@ -3,7 +3,7 @@
 tag=${1:-r03_4k}
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
-ARGS="--height 2160 --width 3840 --dataset underwater --cpu-baseline none --frames 3"
+ARGS="--height 2160 --width 3840 --dataset underwater --cpu-baseline none --frames 3 --full"
 step() {
   local lim=$1 log=$2; shift 2
   timeout -k 10 $lim "$@" > $log 2>&1

@@ -3,13 +3,14 @@
 set -e
 tag=${1:-prof}
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
-rm -rf $R/gpurun_out/$tag
+OUT=${OUT:-$R/out}      # absolute: the profiled runs start from /tmp
+mkdir -p $OUT
+rm -rf $OUT/$tag
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$tag -o out -- python3 $R/bench.py --steps 3 --warmup 2 --cpu-baseline none > $R/gpurun_out/${tag}_bench.json 2> $R/gpurun_out/${tag}_bench.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$tag -o out -- python3 $R/bench.py --full --steps 3 --warmup 2 --cpu-baseline none > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err
 cd $R
-f=$(find gpurun_out/$tag -name "*kernel_stats.csv" | sort | tail -1)
-cp $f gpurun_out/${tag}_kernel_stats.csv
-head -40 gpurun_out/${tag}_kernel_stats.csv | cut -c1-150
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --cpu-baseline none > gpurun_out/${tag}_unprofiled.json 2>/dev/null
-cat gpurun_out/${tag}_unprofiled.json | cut -c1-200
+f=$(find $OUT/$tag -name "*kernel_stats.csv" | sort | tail -1)
+cp $f $OUT/${tag}_kernel_stats.csv
+head -40 $OUT/${tag}_kernel_stats.csv | cut -c1-150
+timeout -k 10 300 python bench.py --steps 20 --warmup 3 --cpu-baseline none > $OUT/${tag}_unprofiled.json 2>/dev/null
+cat $OUT/${tag}_unprofiled.json | cut -c1-200
