@@ -48,7 +48,7 @@ int zt_texture_mask_f32(const float* a, const float* b, float* mask, float* rati
 int zt_ycc_flat_f32(const float* src, float* dst, long long nelem, zt_stream_t stream);
 
 
-/* ---- MFMA implicit-GEMM convolution family (zt_conv.hip) -----------------------------------------------------
+/* ---- MFMA implicit-GEMM convolution family (zt_conv*.hip, zt_wgrad.hip) --------------------------------
  * Replaces F.conv2d of model.py:20-27, 36-43, 55-80, every conv of model/RAFT/{extractor,update}.py, and (as a 1x1
  * conv whose "weights" are fmap2) the all-pairs matmul of corr.py:52-60.
  * x: nhwc [N][H][W][ldx] (first Cin channels used; channels >= csplit come from x2 [..][ldx2] when x2 != NULL);

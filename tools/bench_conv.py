@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Tuning tool (GPU box): time the bf16 convolution variants on the 1080p Enhancer layer, with ablations."""
+"""Tuning tool (GPU box): time the bf16 convolution variants (1 ws, 2 tiled, 3 register-stationary) on the 1080p Enhancer layers."""
 import importlib
 import sys
 import os
@@ -32,26 +32,20 @@ def run(cin, cout, k, variant, epi=0, iters=10):
 
 
 AB_MODE = os.environ.get("ZT_BENCH_AB")
-names = {3: "register-stationary", 33: "rs no-mfma", 34: "rs no-store", 36: "rs no-halo", 38: "rs mfma only", 39: "rs barriers only", 1: "ws full", 2: "tiled"}
+names = {3: "register-stationary", 1: "ws full", 2: "tiled"}
 ONLY = os.environ.get("ZT_BENCH_ONLY")
 if ONLY:          # one variant of one layer, for counter collection: ZT_BENCH_ONLY="64,64,3[,epi]"
     t = [int(v) for v in ONLY.split(",")]
     print("c%d->%d variant %d epi %d: %7.1f us" % (t[0], t[1], t[2], t[3] if len(t) > 3 else 0, run(t[0], t[1], 3, t[2], epi=t[3] if len(t) > 3 else 0, iters=30)), flush=True)
     sys.exit(0)
-ABL = os.environ.get("ZT_BENCH_ABL")
-if ABL:           # phase ablations of the register-stationary kernel on one layer: ZT_BENCH_ABL="9,64"
-    cin, cout = (int(t) for t in ABL.split(","))
-    for v in (3, 33, 34, 36, 38, 39):
-        print("c%d->%d  %-22s %7.1f us" % (cin, cout, names[v], run(cin, cout, 3, v, iters=30)), flush=True)
-    sys.exit(0)
-if AB_MODE:      # A/B of two variants, interleaved, many iterations: ZT_BENCH_AB="3,40"
+if AB_MODE:      # A/B of two variants, interleaved, many iterations: ZT_BENCH_AB="3,1"
     va, vb = (int(t) for t in AB_MODE.split(","))
     for (cin, cout) in ((64, 64), (48, 48)):
         for rep in range(3):
             print("c%d->%d  variant %d: %7.1f us   variant %d: %7.1f us" % (cin, cout, va, run(cin, cout, 3, va, iters=60), vb, run(cin, cout, 3, vb, iters=60)), flush=True)
     sys.exit(0)
 for (cin, cout, k) in ((64, 64, 3), (48, 48, 3)):
-    for v in (3, 33, 34, 36, 38, 39, 1):
+    for v in (3, 1, 2):
         print("c%d->%d k%d  %-24s %8.1f us" % (cin, cout, k, names[v], run(cin, cout, k, v)), flush=True)
 print("c64->64 k3 ws full + residual epi %8.1f us" % run(64, 64, 3, 1, epi=3))
 print("c64->64 k3 rs + residual epi      %8.1f us" % run(64, 64, 3, 3, epi=3))

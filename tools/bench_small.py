@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Tuning tool (GPU box): where do the 11-16 us of a small-map (45 x 80) RAFT convolution go?  Times one layer back-to-back (warm
-instruction cache, weights in L2) with phase ablations of the tiled kernel (variant 64 + bits: 2 no epilogue, 4 no K loop, 8 empty kernel,
-16 K range walked four times), and the same layers alternated (cold instruction cache, as inside the refinement loop)."""
+"""Tuning tool (GPU box): the small-map (45 x 80) RAFT convolutions of the tiled kernel.  Times one layer back-to-back (warm
+instruction cache, weights in L2), and the same layers alternated (cold instruction cache, as inside the refinement loop)."""
 import importlib
 import os
 import sys
@@ -46,17 +45,14 @@ layers = {"gru 1x5 384->256 sigmoid": Layer(384, 256, 1, 5, "sigmoid"), "3x3 256
           "1x1 328->256 relu": Layer(328, 256, 1, 1), "7x7 8->128 relu": Layer(2, 128, 7, 7), "3x3 256->2": Layer(256, 2, 3, 3, None)}
 g = torch.cuda.CUDAGraph()
 for name, L in layers.items():
-    row = []
-    for v, tag in ((2, "full"), (66, "no-epilogue"), (68, "no-K-loop"), (70, "prologue-only"), (72, "empty"), (80, "K x4")):
-        # replay 50 launches from a hipGraph: no host launch cost in the number
-        L.launch(v)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for _ in range(50):
-                L.launch(v)
-        row.append("%s %5.1f" % (tag, timed(g.replay, 20) / 50))
-    print("%-26s back-to-back (graph): %s us" % (name, " | ".join(row)), flush=True)
+    # replay 50 launches from a hipGraph: no host launch cost in the number
+    L.launch(2)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(50):
+            L.launch(2)
+    print("%-26s back-to-back (graph): full %5.1f us" % (name, timed(g.replay, 20) / 50), flush=True)
 ls = list(layers.values())
 g = torch.cuda.CUDAGraph()
 with torch.cuda.graph(g):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Tuning tool (GPU box): the bf16 weight-gradient kernels on the 1080p layers (env knobs: ZT_WGRAD_NW4, ZT_WGRAD_BLOCKS)."""
+"""Tuning tool (GPU box): the bf16 weight-gradient kernels on the 1080p layers (env knobs: ZT_WGRAD_DMA, ZT_WGRAD_BLOCKS)."""
 import importlib
 import os
 import sys

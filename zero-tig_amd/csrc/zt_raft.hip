@@ -1,7 +1,7 @@
 // RAFT-specific kernels of Network.update_cache (reference model/model.py:221-259): input preparation (bilinear
 // down-scale, uint8 truncation + histogram equalisation, replicate padding), correlation pyramid + fused 4-level
 // 9x9 lookup (model/RAFT/corr.py:12-50), SepConvGRU point-wise stages (update.py:33-60), flow bookkeeping and the
-// convex 8x up-sampling (raft.py:64-75).  Convolutions / the correlation GEMM live in zt_conv.hip.
+// convex 8x up-sampling (raft.py:64-75).  Convolutions / the correlation GEMM live in zt_conv_tiled.hip.
 #include "zt_common.h"
 
 namespace {

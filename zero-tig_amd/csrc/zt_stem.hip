@@ -14,7 +14,7 @@ namespace {
 
 constexpr int ST_TOH = 4, ST_TOW = 32;                 // output tile: one row per wave, two 16-pixel MFMA tiles per wave
 constexpr int ST_IR = 2 * ST_TOH + 5, ST_IC = 72;      // input rows / pixels staged (2 * 32 + 5 = 69 used, + the padding tap)
-constexpr int ST_WP = 80;                              // weight row pitch (elements): conflict-free ds_read_b128 (see zt_conv.hip)
+constexpr int ST_WP = 80;                              // weight row pitch (elements): conflict-free ds_read_b128 (see zt_conv_tiled.hip)
 constexpr int ST_NT = 2;                               // 32 couts per workgroup
 
 __global__ void __launch_bounds__(256) stem7x7s2_bf16_kernel(const zt_bf16* __restrict__ x, int H, int W, const zt_bf16* __restrict__ w,

@@ -231,7 +231,7 @@ class Ops:
         sq = int(out.item())
         return float("inf") if sq == 0 else 10.0 * math.log10(255.0 ** 2 * n / sq)
 
-    # ---- convolution family (zt_conv.hip) ---------------------------------------------------------------------
+    # ---- convolution family (zt_conv*.hip, zt_wgrad.hip) ------------------------------------------------
     def repack_weight(self, w, ldw=None, co_off=0, transpose_flip=False, out=None):
         """torch [Cout,Cin,KH,KW] -> device layout [KH*KW, Cin', ldw]."""
         _f32c(w)
