@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Inference + PSNR against ground truth -- the PSNR leg of the reference evals.py (flags evals.py:26-39, loop 107-170, metric
-83-85, summary 184-192) with the metric computed on the device as an exact integer reduction.  SSIM (skimage), LPIPS (lpips /
-VGG weights) and histogram matching (skimage) are third-party and absent here: their fields are written as null.
+"""Inference + PSNR / SSIM against ground truth, before and after histogram matching -- the reference evals.py (flags
+evals.py:26-39, loop 107-170, metrics 83-87, matching 100-103, summary 184-192) with every metric computed on the device: PSNR
+as an exact integer reduction, SSIM from integer window sums in fp64, histogram matching (all channels pooled, as skimage's
+default does it) by a radix sort of the output.  LPIPS (lpips / VGG weights) is third-party and absent: its fields are null.
 Ground truth: `<...>/input/<scene>/low_light_*/N.png` -> `<...>/gt/<scene>/normal_light_*/N.png` (evals.py:122)."""
 import argparse
 import json
@@ -28,6 +29,7 @@ parser.add_argument("--of_scale", type=int, default=3)
 parser.add_argument("--dataset", type=str, default="RLV")
 parser.add_argument("--gain", type=int, default=100, help="kept for CLI compatibility (unused upstream as well)")
 parser.add_argument("--save_images", type=int, default=20, help="write the first N result pairs (evals.py:162)")
+parser.add_argument("--hist_match", type=int, default=1, help="0: skip histogram matching and the *_HM metrics (evals.py:114)")
 
 
 def main():
@@ -35,6 +37,10 @@ def main():
     os.makedirs(args.save, exist_ok=True)
     logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(asctime)s %(message)s", datefmt="%m/%d %I:%M:%S %p")
     logging.getLogger().addHandler(logging.FileHandler(os.path.join(args.save, "log.txt")))
+    # Finetunemodel builds its RAFT after the weights file is read (model.py:268-290), i.e. with freshly drawn weights: seed them,
+    # as train.py does, so that two evaluations of one weights file report the same numbers
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
     dev = torch.device("cuda", args.gpu)
     args.device_ingest = True                      # loaders decode only; resize + ToTensor (multi_read_data.py:127-132) on the GPU
     test_set = CreateDataset(args, task="test")
@@ -43,6 +49,7 @@ def main():
     model = Finetunemodel(args).to(dev)
     model.eval()
     total, n = 0.0, 0
+    total_ssim, total_hm, total_ssim_hm = 0.0, 0.0, 0.0
     with torch.no_grad():
         for i, (inp, img_name, img_path, last_img_path) in enumerate(queue):
             model.is_new_seq = i == 0 or utils.sequential_judgment(img_path[0], last_img_path[0])
@@ -52,7 +59,16 @@ def main():
             gt_t = utils.ingest_frame(gt, dev)                     # same resize to 1920 x 1080 + ToTensor as the inputs, on the device
             psnr = utils.psnr(output, gt_t)                        # evals.py:83-85, exact integer sum on the device
             total, n = total + psnr, n + 1
-            logging.info("NUM: %d, PSNR: %.3f, Total PSNR: %.3f", n, psnr, total / n)
+            ssim = utils.ssim(output, gt_t)                        # evals.py:87
+            total_ssim += ssim
+            logging.info("NUM: %d, PSNR: %.3f, SSIM: %.3f", n, psnr, ssim)
+            logging.info("Total PSNR: %.3f, Total SSIM: %.3f", total / n, total_ssim / n)
+            if args.hist_match:
+                hm = utils.histogram_match(output, gt_t)           # evals.py:100-103, 158-159
+                psnr_hm, ssim_hm = utils.psnr(hm, gt_t), utils.ssim(hm, gt_t)
+                total_hm, total_ssim_hm = total_hm + psnr_hm, total_ssim_hm + ssim_hm
+                logging.info("NUM: %d, PSNR_HM: %.3f, SSIM_HM: %.3f", n, psnr_hm, ssim_hm)
+                logging.info("Total PSNR_HM: %.3f, Total SSIM_HM: %.3f", total_hm / n, total_ssim_hm / n)
             if i < args.save_images:
                 parts = img_path[0].split(os.sep)
                 save_dir = os.path.join(args.save, parts[-3] + "/" + parts[-2])
@@ -60,8 +76,13 @@ def main():
                 name = img_name[0].split("/")[-1].split(".")[0]
                 Image.fromarray(utils.quantize_u8(output).cpu().numpy()).save(save_dir + "/" + name + "_denoise.png", "PNG")
                 Image.fromarray(utils.quantize_u8(enhance).cpu().numpy()).save(save_dir + "/" + name + "_enhance.png", "PNG")
+                if args.hist_match:                                # evals.py:178-181: np.round(x * 255), written as RGB
+                    Image.fromarray(utils.quantize_u8(hm, round_half_even=True).cpu().numpy()).save(
+                        save_dir + "/" + name + "_denoise_hm.png", "PNG")
     with open(os.path.join(args.save, "Metrics.json"), "w") as fh:
-        json.dump({"Total_PSNR": total / max(n, 1), "Total_SSIM": None, "Total_LPIPS": None, "Total_PSNR_HM": None, "Total_SSIM_HM": None,
+        hm_on = bool(args.hist_match)
+        json.dump({"Total_PSNR": total / max(n, 1), "Total_SSIM": total_ssim / max(n, 1), "Total_LPIPS": None,
+                   "Total_PSNR_HM": total_hm / max(n, 1) if hm_on else None, "Total_SSIM_HM": total_ssim_hm / max(n, 1) if hm_on else None,
                    "Total_LPIPS_HM": None, "images": n}, fh)
 
 

@@ -236,6 +236,21 @@ int zt_quantize_u8_hwc(const float* src, unsigned char* dst, int H, int W, int m
 int zt_sqdiff_u8_f32(const float* a, const float* b, long long n, unsigned long long* partial, int nblk, unsigned long long* out,
                      zt_stream_t stream);
 
+/* Evaluation metrics of evals.py (zt_metrics.hip).
+ * zt_ssim_u8_f32: out[0] = skimage structural_similarity(round(a*255), round(b*255), channel_axis=2, data_range=255) of two planar
+ *   fp32 [3][H][W] frames (evals.py:87): 7x7 uniform window, sample covariance, 3-pixel border cropped, mean over the pixels of a
+ *   channel, then over the channels.  Window sums are exact integers, the rest is fp64 in a fixed order (same input, same bits).
+ *   partial: npartial x 8 bytes of workspace, npartial >= 3 * ceil((H-6)/32) * ceil((W-6)/64).  H < 7 or W < 7: ZT_EINVAL.
+ * zt_match_histograms_f32: out = skimage exposure.match_histograms(src, tmpl) with channel_axis=None (evals.py:100-103: the values
+ *   of all channels pooled into ONE distribution), bit for bit: out_i = float(interp(cnt_i / n, tq, tv)) in fp64, cnt_i = number of
+ *   source values <= src_i (-0.0 == +0.0), tq / tv = cumulative share / value of the occupied levels of round(tmpl*255).
+ *   src, out: n finite fp32 values, 16-byte aligned; tmpl: m fp32 values k/255 (a ToTensor image), any m >= 1.
+ *   scratch: 16-byte aligned workspace of at least 8 * ((n+3) & ~3) + 1024 * ceil(n/4096) + 8192 bytes (two key buffers of the
+ *   radix sort, its digit counts, the template table). */
+int zt_ssim_u8_f32(const float* a, const float* b, int H, int W, double* partial, int npartial, double* out, zt_stream_t stream);
+int zt_match_histograms_f32(const float* src, long long n, const float* tmpl, long long m, float* out, void* scratch,
+                            size_t scratch_bytes, zt_stream_t stream);
+
 
 /* ---- input side (zt_ingest.hip): dataloader/multi_read_data.py:127-132 on the device -------------------------------------
  * The loader workers decode to interleaved uint8 RGB [H][W][3]; `im.resize((1920, 1080))` (PIL default filter for RGB = BICUBIC,

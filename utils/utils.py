@@ -121,6 +121,18 @@ def psnr(img, gt):
     return _ops().psnr_u8(_prep(img), _prep(gt))
 
 
+def ssim(img, gt):
+    """evals.py:87: skimage `ssim(np.round(img * 255), np.round(gt * 255), channel_axis=2, data_range=255)` on the device
+    (integer window sums, fp64 from there on)."""
+    return _ops().ssim_u8(_prep(img), _prep(gt))
+
+
+def histogram_match(out, gt):
+    """evals.py:100-103: `exposure.match_histograms(out, gt)` on the device.  As in the reference the three channels are pooled
+    into one distribution (skimage's channel_axis=None default); the result is bit-identical to skimage's."""
+    return _ops().match_histograms(_prep(out), _prep(gt))
+
+
 def count_parameters_in_MB(model):                           # utils.py:81-82
     return sum(int(np.prod(v.size())) for name, v in model.named_parameters() if "auxiliary" not in name) / 1e6
 

@@ -26,6 +26,15 @@ __device__ __forceinline__ float zt_clampf(float v, float lo, float hi) {
   return fminf(fmaxf(v, lo), hi);
 }
 
+// float in [0, 1] -> 8-bit level, the two ways the reference scripts do it (zt_io.hip, zt_metrics.hip)
+__device__ __forceinline__ int zt_quant_u8(float v, int mode) {
+  const float s = v * 255.f;
+  if (mode == 0) return (int)fminf(fmaxf(s, 0.f), 255.f);       // np.clip then C truncation
+  // np.round(..).astype(np.uint8): round half to even, then the wrap-around of a uint8 cast (values are clamped upstream to
+  // [1e-4, 1], so the wrap never triggers; it is reproduced anyway)
+  return (int)rintf(s) & 255;
+}
+
 __device__ __forceinline__ float zt_wave_sum(float v) {
   v += __shfl_xor(v, 32);
   v += __shfl_xor(v, 16);

@@ -8,14 +8,6 @@
 
 namespace {
 
-__device__ __forceinline__ int quant_u8(float v, int mode) {
-  const float s = v * 255.f;
-  if (mode == 0) return (int)fminf(fmaxf(s, 0.f), 255.f);       // np.clip then C truncation
-  // np.round(..).astype(np.uint8): round half to even, then the wrap-around of a uint8 cast (values are clamped upstream to
-  // [1e-4, 1], so the wrap never triggers; it is reproduced anyway)
-  return (int)rintf(s) & 255;
-}
-
 // planar fp32 [3][H][W] -> interleaved uint8 [H][W][3]; thread = 4 pixels = 12 output bytes = three 4-byte stores
 __global__ void __launch_bounds__(256) quantize_hwc_kernel(const float* __restrict__ src, unsigned* __restrict__ dst, long long HW,
                                                            int mode) {
@@ -27,7 +19,7 @@ __global__ void __launch_bounds__(256) quantize_hwc_kernel(const float* __restri
   for (int j = 0; j < 4; ++j) {
     const long long pp = p + j < HW ? p + j : HW - 1;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) b[j * 3 + c] = (unsigned char)quant_u8(src[(size_t)c * HW + pp], mode);
+    for (int c = 0; c < 3; ++c) b[j * 3 + c] = (unsigned char)zt_quant_u8(src[(size_t)c * HW + pp], mode);
   }
   if (p + 4 <= HW) {
 #pragma unroll
@@ -45,7 +37,7 @@ __global__ void __launch_bounds__(256) sqdiff_u8_kernel(const float* __restrict_
   __shared__ unsigned long long red[256];
   unsigned long long s = 0;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const int d = quant_u8(a[i], 1) - quant_u8(b[i], 1);
+    const int d = zt_quant_u8(a[i], 1) - zt_quant_u8(b[i], 1);
     s += (unsigned long long)(d * d);
   }
   red[threadIdx.x] = s;

@@ -231,6 +231,29 @@ class Ops:
         sq = int(out.item())
         return float("inf") if sq == 0 else 10.0 * math.log10(255.0 ** 2 * n / sq)
 
+    def ssim_u8(self, a, b):
+        """evals.py:87: skimage structural_similarity(round(a*255), round(b*255), channel_axis=2, data_range=255) of two
+        [1,3,H,W] frames -> python float; fp64 on the device, one 8-byte read-back."""
+        _f32c(a), _f32c(b)
+        assert a.dim() == 4 and a.shape[0] == 1 and a.shape[1] == 3 and a.shape == b.shape, (a.shape, b.shape)
+        H, W = int(a.shape[2]), int(a.shape[3])
+        npart = 3 * max(1, -(-(H - 6) // 32)) * max(1, -(-(W - 6) // 64))
+        part = torch.empty(npart, dtype=torch.float64, device=a.device)
+        out = torch.empty(1, dtype=torch.float64, device=a.device)
+        self.lib.call("zt_ssim_u8_f32", a, b, H, W, part, npart, out, self._s(a))
+        return float(out.item())
+
+    def match_histograms(self, src, tmpl):
+        """evals.py:100-103: skimage exposure.match_histograms(src, tmpl), all channels pooled (its channel_axis=None default)
+        -> fp32 tensor of src's shape on the device.  tmpl is a ToTensor image (values k/255) of any size."""
+        _f32c(src), _f32c(tmpl)
+        n, m = src.numel(), tmpl.numel()
+        out = torch.empty_like(src)
+        nbytes = 8 * ((n + 3) & ~3) + 1024 * (-(-n // 4096)) + 8192
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+        self.lib.call("zt_match_histograms_f32", src, n, tmpl, m, out, scratch, nbytes, self._s(src))
+        return out
+
     # ---- convolution family (zt_conv*.hip, zt_wgrad.hip) ------------------------------------------------
     def repack_weight(self, w, ldw=None, co_off=0, transpose_flip=False, out=None):
         """torch [Cout,Cin,KH,KW] -> device layout [KH*KW, Cin', ldw]."""
