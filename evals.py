@@ -2,7 +2,8 @@
 """Inference + PSNR / SSIM against ground truth, before and after histogram matching -- the reference evals.py (flags
 evals.py:26-39, loop 107-170, metrics 83-87, matching 100-103, summary 184-192) with every metric computed on the device: PSNR
 as an exact integer reduction, SSIM from integer window sums in fp64, histogram matching (all channels pooled, as skimage's
-default does it) by a radix sort of the output.  LPIPS (lpips / VGG weights) is third-party and absent: its fields are null.
+default does it) by a radix sort of the output.  LPIPS (VGG, evals.py:73-80, 92-98) is computed when --lpips_weights names the
+user's `lpips.LPIPS(net='vgg').state_dict()` file (zero-tig_amd/lpips.py); without it the two LPIPS fields are null.
 Ground truth: `<...>/input/<scene>/low_light_*/N.png` -> `<...>/gt/<scene>/normal_light_*/N.png` (evals.py:122)."""
 import argparse
 import json
@@ -30,6 +31,9 @@ parser.add_argument("--dataset", type=str, default="RLV")
 parser.add_argument("--gain", type=int, default=100, help="kept for CLI compatibility (unused upstream as well)")
 parser.add_argument("--save_images", type=int, default=20, help="write the first N result pairs (evals.py:162)")
 parser.add_argument("--hist_match", type=int, default=1, help="0: skip histogram matching and the *_HM metrics (evals.py:114)")
+parser.add_argument("--lpips_weights", type=str, default=None,
+                    help="torch.save(lpips.LPIPS(net='vgg').state_dict(), FILE); default: no LPIPS (fields null)")
+parser.add_argument("--lpips_precision", type=str, default="fp32", choices=["fp32", "bf16"])
 
 
 def main():
@@ -50,6 +54,8 @@ def main():
     model.eval()
     total, n = 0.0, 0
     total_ssim, total_hm, total_ssim_hm = 0.0, 0.0, 0.0
+    lpips_model = utils.lpips_model(args.lpips_weights, dev, args.lpips_precision) if args.lpips_weights else None
+    total_lpips, total_lpips_hm = 0.0, 0.0
     with torch.no_grad():
         for i, (inp, img_name, img_path, last_img_path) in enumerate(queue):
             model.is_new_seq = i == 0 or utils.sequential_judgment(img_path[0], last_img_path[0])
@@ -61,14 +67,28 @@ def main():
             total, n = total + psnr, n + 1
             ssim = utils.ssim(output, gt_t)                        # evals.py:87
             total_ssim += ssim
-            logging.info("NUM: %d, PSNR: %.3f, SSIM: %.3f", n, psnr, ssim)
-            logging.info("Total PSNR: %.3f, Total SSIM: %.3f", total / n, total_ssim / n)
+            if lpips_model is None:
+                logging.info("NUM: %d, PSNR: %.3f, SSIM: %.3f", n, psnr, ssim)
+                logging.info("Total PSNR: %.3f, Total SSIM: %.3f", total / n, total_ssim / n)
+            else:                                                  # evals.py:92-98, 153-157; the ground truth's features serve both calls
+                gt_feat = lpips_model.features(gt_t)
+                lp = utils.lpips(output, gt_feat, lpips_model)
+                total_lpips += lp
+                logging.info("NUM: %d, PSNR: %.3f, SSIM: %.3f, LPIPS: %.3f", n, psnr, ssim, lp)
+                logging.info("Total PSNR: %.3f, Total SSIM: %.3f, Total LPIPS: %.3f", total / n, total_ssim / n, total_lpips / n)
             if args.hist_match:
                 hm = utils.histogram_match(output, gt_t)           # evals.py:100-103, 158-159
                 psnr_hm, ssim_hm = utils.psnr(hm, gt_t), utils.ssim(hm, gt_t)
                 total_hm, total_ssim_hm = total_hm + psnr_hm, total_ssim_hm + ssim_hm
-                logging.info("NUM: %d, PSNR_HM: %.3f, SSIM_HM: %.3f", n, psnr_hm, ssim_hm)
-                logging.info("Total PSNR_HM: %.3f, Total SSIM_HM: %.3f", total_hm / n, total_ssim_hm / n)
+                if lpips_model is None:
+                    logging.info("NUM: %d, PSNR_HM: %.3f, SSIM_HM: %.3f", n, psnr_hm, ssim_hm)
+                    logging.info("Total PSNR_HM: %.3f, Total SSIM_HM: %.3f", total_hm / n, total_ssim_hm / n)
+                else:                                              # evals.py:158-165: the float matched frame, not its quantised form
+                    lp_hm = utils.lpips(hm, gt_feat, lpips_model)
+                    total_lpips_hm += lp_hm
+                    logging.info("NUM: %d, PSNR_HM: %.3f, SSIM_HM: %.3f, LPIPS_HM: %.3f", n, psnr_hm, ssim_hm, lp_hm)
+                    logging.info("Total PSNR_HM: %.3f, Total SSIM_HM: %.3f, Total LPIPS_HM: %.3f", total_hm / n, total_ssim_hm / n,
+                                 total_lpips_hm / n)
             if i < args.save_images:
                 parts = img_path[0].split(os.sep)
                 save_dir = os.path.join(args.save, parts[-3] + "/" + parts[-2])
@@ -81,9 +101,11 @@ def main():
                         save_dir + "/" + name + "_denoise_hm.png", "PNG")
     with open(os.path.join(args.save, "Metrics.json"), "w") as fh:
         hm_on = bool(args.hist_match)
-        json.dump({"Total_PSNR": total / max(n, 1), "Total_SSIM": total_ssim / max(n, 1), "Total_LPIPS": None,
+        lp_on = lpips_model is not None
+        json.dump({"Total_PSNR": total / max(n, 1), "Total_SSIM": total_ssim / max(n, 1),
+                   "Total_LPIPS": total_lpips / max(n, 1) if lp_on else None,
                    "Total_PSNR_HM": total_hm / max(n, 1) if hm_on else None, "Total_SSIM_HM": total_ssim_hm / max(n, 1) if hm_on else None,
-                   "Total_LPIPS_HM": None, "images": n}, fh)
+                   "Total_LPIPS_HM": total_lpips_hm / max(n, 1) if lp_on and hm_on else None, "images": n}, fh)
 
 
 if __name__ == "__main__":

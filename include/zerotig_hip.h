@@ -252,6 +252,28 @@ int zt_match_histograms_f32(const float* src, long long n, const float* tmpl, lo
                             size_t scratch_bytes, zt_stream_t stream);
 
 
+/* ---- LPIPS (VGG16, lpips 0.1) of evals.py:73-80, 92-98 (zt_lpips.hip) ------------------------------------------------------
+ * zt_conv3x3_wide_bf16: y = [relu](conv3x3(x) + bias), stride 1, pad 1, for wide layers: x bf16 nhwc [N][H][W][ldx], w bf16
+ *   [9][CoutP][ldk] (zt_repack_conv_weight_bf16), y bf16 nhwc [N][H][W][ldy], fp32 accumulation.  Cin a multiple of 64, Cout a
+ *   multiple of 128 (anything else: 1001), any H, W >= 1; ldx, ldk, ldy multiples of 8, pointers 16-byte aligned (bias too),
+ *   N*H*W*ldx < 2^31.  A workgroup owns 8 x 16 pixels x 128 couts (VGG16's conv2_1 .. conv5_3; the 3 -> 64 and 64 -> 64 layers in
+ *   front of them are zt_conv2d_nhwc_bf16's).
+ * zt_lpips_prep: planar fp32 [3][H][W] in [0,1] -> nhwc [H][W][8] (dt 0 fp32 / 1 bf16), channel c = ((a - 0.5) * 2 - shift_c) /
+ *   scale_c with lpips' ScalingLayer constants shift = (-.030, -.088, -.188), scale = (.458, .448, .450); channels 3..7 = 0.
+ * zt_maxpool2_nhwc: 2x2 max pool, stride 2, floor (nn.MaxPool2d(2, 2)): [N][H][W][ldx] -> [N][H/2][W/2][ldy], first C channels,
+ *   C a multiple of 4 (fp32) / 8 (bf16), as are ldx and ldy.
+ * zt_lpips_layer: out[0] = mean over the npix pixels of sum_c w[c] (fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10))^2, |f| the
+ *   channel norm of the pixel (lpips normalize_tensor, the 1x1 `lin` layer, spatial_average), for two nhwc maps of C in {64, 128,
+ *   256, 512} channels (strides lda, ldb).  fp32 per pixel, fp64 sums in a fixed order (same input, same bits).
+ *   partial: npartial x 8 bytes of workspace (npartial >= 1; 2048 is never exceeded). */
+int zt_conv3x3_wide_bf16(const void* x, int ldx, int N, int H, int W, int Cin, const void* w, int CoutP, int ldk, const float* bias,
+                         void* y, int ldy, int Cout, int relu, zt_stream_t stream);
+int zt_lpips_prep(const float* src, void* dst, int dt, int H, int W, zt_stream_t stream);
+int zt_maxpool2_nhwc(const void* x, int dt, int ldx, int N, int H, int W, int C, void* y, int ldy, zt_stream_t stream);
+int zt_lpips_layer(const void* fa, int lda, const void* fb, int ldb, int dt, long long npix, int C, const float* w, double* partial,
+                   int npartial, double* out, zt_stream_t stream);
+
+
 /* ---- input side (zt_ingest.hip): dataloader/multi_read_data.py:127-132 on the device -------------------------------------
  * The loader workers decode to interleaved uint8 RGB [H][W][3]; `im.resize((1920, 1080))` (PIL default filter for RGB = BICUBIC,
  * Pillow's 8-bit two-pass resampler) and `transforms.ToTensor()` run here, bit-identical to the host libraries.

@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--num_workers", type=int, default=0)
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node used for training (frame-clip data parallel over RCCL)")
+    ap.add_argument("--lpips_weights", type=str, default=None, help="passed to evals.py: LPIPS (VGG) weights file; default: no LPIPS")
+    ap.add_argument("--lpips_precision", type=str, default="fp32", choices=["fp32", "bf16"])
     a = ap.parse_args()
     os.makedirs(a.base_exp_dir, exist_ok=True)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s",
@@ -66,8 +68,9 @@ def main():
             log.error("Final weights file not found at %s. Skipping.", weights)
             ok_all = False
             continue
+        lpips_args = ["--lpips_weights", a.lpips_weights, "--lpips_precision", a.lpips_precision] if a.lpips_weights else []
         if not run([sys.executable, os.path.join(here, "evals.py"), "--dataset", dtype, "--lowlight_images_path", data, "--model_pretrain", weights,
-                    "--save", eval_dir], log):
+                    "--save", eval_dir] + lpips_args, log):
             log.error("Evaluation failed for %s.", name)
             ok_all = False
             continue

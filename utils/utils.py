@@ -133,6 +133,20 @@ def histogram_match(out, gt):
     return _ops().match_histograms(_prep(out), _prep(gt))
 
 
+def lpips_model(path, device, precision="fp32"):
+    """evals.py:73-80 `lpips.LPIPS(net='vgg')` on the device from the user's weights file (`torch.save(lpips.LPIPS(net='vgg')
+    .state_dict(), path)`; torchvision's `features.<idx>.*` names are accepted for the convs).  precision: "fp32" or "bf16"."""
+    mod = importlib.import_module("zero-tig_amd.lpips")
+    return mod.LpipsVGG(_ops(), torch.load(path, map_location="cpu"), device, precision)
+
+
+def lpips(img, gt, model):
+    """evals.py:92-98: `loss_fn_vgg(cvt(img), cvt(gt))` of two [1,3,H,W] frames in [0,1] -> python float.  gt may be the list
+    `model.features(gt)` returned earlier (evals.py grades the plain and the matched output against one ground truth)."""
+    gt_feat = gt if isinstance(gt, (list, tuple)) else model.features(_prep(gt))
+    return model.distance(model.features(_prep(img)), gt_feat)[0]
+
+
 def count_parameters_in_MB(model):                           # utils.py:81-82
     return sum(int(np.prod(v.size())) for name, v in model.named_parameters() if "auxiliary" not in name) / 1e6
 

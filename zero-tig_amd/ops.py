@@ -254,6 +254,45 @@ class Ops:
         self.lib.call("zt_match_histograms_f32", src, n, tmpl, m, out, scratch, nbytes, self._s(src))
         return out
 
+    # ---- LPIPS (zt_lpips.hip) -----------------------------------------------------------------------------------
+    def lpips_prep(self, img, dtype=torch.float32):
+        """[1,3,H,W] fp32 in [0,1] -> nhwc [1,H,W,8] (fp32 or bf16): (img - 0.5) * 2 through lpips' scaling layer; channels 3..7 zero."""
+        _f32c(img)
+        assert img.dim() == 4 and img.shape[0] == 1 and img.shape[1] == 3, img.shape
+        H, W = int(img.shape[2]), int(img.shape[3])
+        out = torch.empty((1, H, W, 8), dtype=dtype, device=img.device)
+        self.lib.call("zt_lpips_prep", img, out, _dt(out), H, W, self._s(img))
+        return out
+
+    def maxpool2(self, x):
+        """nn.MaxPool2d(2, 2) of a CV/tensor NHWC (fp32 or bf16) -> [N, H // 2, W // 2, C]"""
+        x = _cv(x)
+        out = torch.empty((x.N, x.H // 2, x.W // 2, x.C), dtype=x.t.dtype, device=x.t.device)
+        self.lib.call("zt_maxpool2_nhwc", x.ptr, _dt(x.t), x.ld, x.N, x.H, x.W, x.C, out, x.C, self._s(x.t))
+        return out
+
+    def conv3x3_wide_bf16(self, x, wdev, bias, Cout, relu=True, out=None):
+        """y = [relu](conv3x3(x) + bias), pad 1, for Cin % 64 == 0 and Cout % 128 == 0: bf16 NHWC in and out, wdev bf16 [9, CoutP, ldk]."""
+        x = _cv(x)
+        assert x.t.dtype == torch.bfloat16 and wdev.dtype == torch.bfloat16 and wdev.shape[0] == 9
+        if out is None:
+            out = torch.empty((x.N, x.H, x.W, Cout), dtype=torch.bfloat16, device=x.t.device)
+        o = _cv(out)
+        assert o.t.dtype == torch.bfloat16 and (o.N, o.H, o.W) == (x.N, x.H, x.W)
+        tok = self._ev_begin(self.profile["match"].get((3, 3, 1, x.C, Cout, x.H, x.W))) if self.profile else None
+        self.lib.call("zt_conv3x3_wide_bf16", x.ptr, x.ld, x.N, x.H, x.W, x.C, wdev, wdev.shape[1], wdev.shape[2], bias, o.ptr, o.ld,
+                      Cout, int(relu), self._s(x.t))
+        self._ev_end(tok)
+        return out
+
+    def lpips_layer(self, fa, fb, w, out):
+        """out[0] (fp64, device) = one tap's LPIPS term of two NHWC feature maps (N == 1, same dtype); w: fp32 [C] lin weights."""
+        fa, fb = _cv(fa), _cv(fb)
+        assert fa.t.dtype == fb.t.dtype and (fa.N, fa.H, fa.W, fa.C) == (fb.N, fb.H, fb.W, fb.C) and fa.N == 1
+        assert w.dtype == torch.float32 and w.numel() == fa.C and out.dtype == torch.float64
+        part = torch.empty(2048, dtype=torch.float64, device=fa.t.device)
+        self.lib.call("zt_lpips_layer", fa.ptr, fa.ld, fb.ptr, fb.ld, _dt(fa.t), fa.H * fa.W, fa.C, w, part, 2048, out, self._s(fa.t))
+
     # ---- convolution family (zt_conv*.hip, zt_wgrad.hip) ------------------------------------------------
     def repack_weight(self, w, ldw=None, co_off=0, transpose_flip=False, out=None):
         """torch [Cout,Cin,KH,KW] -> device layout [KH*KW, Cin', ldw]."""
