@@ -34,6 +34,10 @@ parser.add_argument("--hist_match", type=int, default=1, help="0: skip histogram
 parser.add_argument("--lpips_weights", type=str, default=None,
                     help="torch.save(lpips.LPIPS(net='vgg').state_dict(), FILE); default: no LPIPS (fields null)")
 parser.add_argument("--lpips_precision", type=str, default="fp32", choices=["fp32", "bf16"])
+parser.add_argument("--precision", type=str, default=None, choices=["fp32", "bf16"],
+                    help="model precision: fp32 = parity mode, bf16 = throughput mode; when not given, ZEROTIG_PRECISION if set, else fp32")
+parser.add_argument("--graph", type=int, default=0, choices=[0, 1],
+                    help="1: drive the loop through InferStep (weights prepared once, steady-state frames replayed as one hipGraph)")
 
 
 def main():
@@ -56,10 +60,18 @@ def main():
     total_ssim, total_hm, total_ssim_hm = 0.0, 0.0, 0.0
     lpips_model = utils.lpips_model(args.lpips_weights, dev, args.lpips_precision) if args.lpips_weights else None
     total_lpips, total_lpips_hm = 0.0, 0.0
+    step = None
+    if args.graph:
+        import importlib
+        step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080))
     with torch.no_grad():
         for i, (inp, img_name, img_path, last_img_path) in enumerate(queue):
-            model.is_new_seq = i == 0 or utils.sequential_judgment(img_path[0], last_img_path[0])
-            enhance, output, illum = model(utils.ingest_frame(inp, dev))   # Finetunemodel.forward updates the recurrent cache itself
+            new_seq = i == 0 or utils.sequential_judgment(img_path[0], last_img_path[0])
+            if step is not None:                   # the tensors live in the step's buffers: everything below reads them before the next call
+                enhance, output, illum = step(inp, new_seq)
+            else:
+                model.is_new_seq = new_seq
+                enhance, output, illum = model(utils.ingest_frame(inp, dev))   # Finetunemodel.forward updates the recurrent cache itself
             gt_path = img_path[0].replace("input", "gt").replace("low_light_", "normal_light_")
             gt = torch.from_numpy(np.asarray(Image.open(gt_path).convert("RGB"), dtype=np.uint8).copy())
             gt_t = utils.ingest_frame(gt, dev)                     # same resize to 1920 x 1080 + ToTensor as the inputs, on the device

@@ -130,6 +130,15 @@ int zt_post_enh_f32(const float* x, const float* s2, const float* L2, const floa
                     float* H2, float* H11, float* H12, float* H1, int H, int W, zt_stream_t stream);
 /* model.py:179-192: (outA|outB) = clamp(cat[A,B] - r, 1e-4, 1), r planar 6ch */
 int zt_clamp_sub6_f32(const float* A, const float* B, const float* r, float* outA, float* outB, long long HW, zt_stream_t stream);
+/* Denoise_1 / Denoise_2 forward and its tail in one launch, bf16 throughput mode (zt_denoise.hip; model.py:15-44, 316, 335-337):
+ *   out[c] = clamp(ref[c] - conv1x1(lrelu(conv3x3(lrelu(conv3x3(cat(s0..)))))) [c], 1e-4, 1),  c < cout
+ * s0..s3: ngroups (1 or 4) planar fp32 [3][H][W] sources, concatenated in order and rounded to bf16 while staged; ref0 (channels
+ * 0..2) / ref1 (channels 3..5, cout == 6 only): the planar fp32 tensors subtracted from, used in fp32.  Weights in the layout of
+ * zt_repack_conv_weight_bf16: w1 [9][48][ldk1] (ldk1 = 8 or 16), w2 [9][48][48], w3 [1][16][48]; biases fp32.  out: planar fp32
+ * [cout][H][W]; res (may be NULL): the residual before the subtraction, same shape.  The 48-channel activations stay on chip. */
+int zt_denoise_fused_bf16(const float* s0, const float* s1, const float* s2, const float* s3, int ngroups, const float* ref0,
+                          const float* ref1, const void* w1, int ldk1, const float* b1, const void* w2, const float* b2,
+                          const void* w3, const float* b3, int cout, float* out, float* res, int H, int W, zt_stream_t stream);
 /* its backward into the nhwc gradient of r */
 int zt_clamp_sub6_bwd(const float* A, const float* B, const float* r, const float* gA, const float* gB, void* dr, int dt, int ld,
                           long long HW, zt_stream_t stream);

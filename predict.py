@@ -24,6 +24,10 @@ parser.add_argument("--seed", type=int, default=2)
 parser.add_argument("--of_scale", type=int, default=3)
 parser.add_argument("--dataset", type=str, default="RLV")
 parser.add_argument("--num_workers", type=int, default=-1, help="decode workers; -1: host cores - 2, at most 12")
+parser.add_argument("--precision", type=str, default=None, choices=["fp32", "bf16"],
+                    help="model precision: fp32 = parity mode, bf16 = throughput mode; when not given, ZEROTIG_PRECISION if set, else fp32")
+parser.add_argument("--graph", type=int, default=0, choices=[0, 1],
+                    help="1: drive the loop through InferStep (weights prepared once, steady-state frames replayed as one hipGraph)")
 
 
 def save_images(tensor):
@@ -36,6 +40,10 @@ def main():
     args = parser.parse_args()
     os.makedirs(args.save, exist_ok=True)
     logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(asctime)s %(message)s")
+    # Finetunemodel builds its RAFT after the weights file is read (model.py:268-290), i.e. with freshly drawn weights: seed them,
+    # as evals.py does, so that two runs over one weights file write the same images
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
     dev = torch.device("cuda", args.gpu)
     args.device_ingest = True                      # loaders decode only; resize + ToTensor (multi_read_data.py:127-132) on the GPU
     test_set = CreateDataset(args, task="test")
@@ -45,10 +53,20 @@ def main():
     model.eval()
     for p in model.parameters():
         p.requires_grad = False
+    step = None
+    if args.graph:
+        import importlib
+        step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080))
     with torch.no_grad():
         for i, (inp, img_name, img_path, last_img_path) in enumerate(queue):
-            model.is_new_seq = i == 0 or sequential_judgment(img_path[0], last_img_path[0])
-            enhance, output, illum = model(utils.ingest_frame(inp, dev))
+            new_seq = i == 0 or sequential_judgment(img_path[0], last_img_path[0])
+            if step is not None:                   # the two uint8 images are made inside the step; valid until the next call
+                step(inp, new_seq)
+                enh_u8, out_u8 = (t.cpu().numpy() for t in step.u8)
+            else:
+                model.is_new_seq = new_seq
+                enhance, output, illum = model(utils.ingest_frame(inp, dev))
+                enh_u8, out_u8 = save_images(enhance), save_images(output)
             if "RLV" == args.dataset:
                 parts = img_path[0].split(os.sep)
                 save_dir = os.path.join(args.save, parts[-3], parts[-2])
@@ -56,8 +74,8 @@ def main():
                 save_dir = os.path.join(args.save, os.path.basename(os.path.split(img_path[0])[0]))
             os.makedirs(save_dir, exist_ok=True)
             name = img_name[0].split("/")[-1].split(".")[0]
-            Image.fromarray(save_images(output)).save(save_dir + "/" + name + "_denoise.png", "PNG")
-            Image.fromarray(save_images(enhance)).save(save_dir + "/" + name + "_enhance.png", "PNG")
+            Image.fromarray(out_u8).save(save_dir + "/" + name + "_denoise.png", "PNG")
+            Image.fromarray(enh_u8).save(save_dir + "/" + name + "_enhance.png", "PNG")
 
 
 if __name__ == "__main__":

@@ -81,12 +81,13 @@ class Engine:
             if pre not in (D1 + ".conv1", "enhance.in_conv.0"):        # inputs of these need no gradient
                 wd[pre + "/T"] = rp(w, transpose_flip=True, out=wd.get(pre + "/T"))
 
-    def _conv(self, x, wkey, bias, cout, k, act=None, out_planar=False, aux=None, epi=0):
-        """stride-1 'same' convolution of the enhancement nets in the engine's precision"""
+    def _conv(self, x, wkey, bias, cout, k, act=None, out_planar=False, aux=None, epi=0, wd=None):
+        """stride-1 'same' convolution of the enhancement nets in the engine's precision (wd: weight table, default self.wd)"""
         pad = (k // 2, k // 2)
+        w = (self.wd if wd is None else wd)[wkey]
         if self.dt:
-            return self.ops.conv2d_bf16(x, self.wd[wkey], bias, cout, k, k, pad, act, out_planar=out_planar, aux=aux, epi=epi)
-        return self.ops.conv2d(x, self.wd[wkey], bias, cout, k, k, 1, pad, act, out_planar=out_planar, aux=aux, epi=epi)
+            return self.ops.conv2d_bf16(x, w, bias, cout, k, k, pad, act, out_planar=out_planar, aux=aux, epi=epi)
+        return self.ops.conv2d(x, w, bias, cout, k, k, 1, pad, act, out_planar=out_planar, aux=aux, epi=epi)
 
     def _wgrad(self, x, dz, cout, k, pre, relu_mask=None):
         """accumulate d loss / d weight and d loss / d bias (column sums of dz, same pass) of conv `pre`.
@@ -335,6 +336,85 @@ class Engine:
         r5 = self._denoise_fwd(D2, [wpH, wps, H2, s2], H, W, 12, 6, "D2c")
         H5p = self._new(1, 6, H, W)
         lib.call("zt_clamp_sub6_f32", H2, s2, r5, H5p, H5p[:, 3:], H * W, s)
+        return H2, H5p[:, :3], H5p[:, 3:]
+
+    # ------------------------------------------------------------------------------------------------ streaming inference
+    STREAM_LAYERS = (D1 + ".conv1", D1 + ".conv2", D1 + ".conv3", D2 + ".conv1", D2 + ".conv2", D2 + ".conv3",
+                     "enhance.in_conv.0", "enhance.conv.0", "enhance.out_conv.0")
+    # bf16 frames of at least this many pixels send a Denoise call to the one-launch kernel (zt_denoise_fused_bf16); smaller
+    # frames keep the pack + three convolutions + tail chain.  Same-process A/B of tools/bench_infer.py, fused vs chain per call
+    # (profiles/infer_540p_1080p_4k.json): 540p D1 64.9 vs 69.9 us, D2 73.9 vs 83.1; 1080p D1 234.7 vs 238.5, D2 251.8 vs 267.7;
+    # 4K D1 883.8 vs 954.0, D2 988.3 vs 1061.0.  No crossover was found down to 540 x 960, the smallest size measured, so the gate
+    # sits there: below it nothing is measured and the chain stays.
+    FUSED_DENOISE_MIN_PIXELS = 540 * 960
+
+    def prepare_stream(self, wp=None):
+        """Frozen-weight preparation of `forward_stream`: the nine convolutions in their device layouts and fp32 bias copies,
+        with the eval-mode BatchNorm folded into enhance.conv.0 (w * scale[cout], b * scale + shift: the recipe RaftPlan uses
+        for the context encoder).  With `wp` given, its buffers are overwritten in place, so their addresses stay valid."""
+        o, p, b = self.ops, self.p, self.buf
+        wp = {} if wp is None else wp
+        rp = o.repack_weight_bf16 if self.dt else o.repack_weight
+        sc, sh, _, _ = o.norm_finalize(None, 1, 64, 1, 2, p["enhance.conv.1.weight"], p["enhance.conv.1.bias"],
+                                       b["enhance.conv.1.running_mean"], b["enhance.conv.1.running_var"], dev=self.dev)
+        for pre in self.STREAM_LAYERS:
+            w, bias = p[pre + ".weight"], p[pre + ".bias"]
+            if pre == "enhance.conv.0":
+                w, bias = w * sc.view(-1, 1, 1, 1), bias * sc.view(-1) + sh.view(-1)
+            wp[pre] = rp(w.float().contiguous(), out=wp.get(pre))
+            if pre + ".bias" in wp:
+                wp[pre + ".bias"].copy_(bias)
+            else:
+                wp[pre + ".bias"] = bias.float().clone()
+        return wp
+
+    def _denoise_stream(self, pre, srcs, refs, wp, H, W, cin, cout, fused=None):
+        """clamp(cat(refs) - Denoise(cat(srcs)), 1e-4, 1) -> planar [1,cout,H,W].  fused: None = route by frame size (bf16 only);
+        True / False force the one-launch kernel / the chain (tools/bench_infer.py times one against the other)"""
+        lib, s = self.lib, self._stream()
+        b1, b2, b3 = wp[pre + ".conv1.bias"], wp[pre + ".conv2.bias"], wp[pre + ".conv3.bias"]
+        if fused is None:
+            fused = bool(self.dt) and H * W >= self.FUSED_DENOISE_MIN_PIXELS
+        if fused:
+            return self.ops.denoise_fused_bf16(srcs, refs, wp[pre + ".conv1"], b1, wp[pre + ".conv2"], b2, wp[pre + ".conv3"], b3, cout)
+        ld = (cin + self.lda - 1) // self.lda * self.lda
+        u = self._pack(ld, H * W, srcs, H, W)
+        a1 = self._conv(CV(u, 0, cin), pre + ".conv1", b1, 48, 3, "lrelu", wd=wp)
+        a2 = self._conv(a1, pre + ".conv2", b2, 48, 3, "lrelu", wd=wp)
+        r = self._conv(a2, pre + ".conv3", b3, cout, 1, None, out_planar=True, wd=wp)
+        out = self._new(1, cout, H, W)
+        if cout == 3:
+            lib.call("zt_ew_f32", refs[0], r, out, 1, 1e-4, 1.0, 3 * H * W, s)
+        else:
+            lib.call("zt_clamp_sub6_f32", refs[0], refs[1], r, out, out[:, 3:], H * W, s)
+        return out
+
+    def forward_stream(self, inp, cache_fn, wp):
+        """`forward_infer` for frozen weights (infer.InferStep): same arithmetic, but the weights come prepared (`prepare_stream`,
+        nothing is repacked per frame), an Enhancer block is ONE launch f <- f + relu(conv'(f) + b') with the BatchNorm folded
+        into conv', and in bf16 mode a Denoise call on a large enough frame is one fused launch.  Returns (H2, H3, s3)."""
+        lib, s = self.lib, self._stream()
+        _, _, H, W = inp.shape
+        self.keep, self.sv, self.training = False, {}, False
+        n3 = 3 * H * W
+        x = self._new(1, 3, H, W)
+        lib.call("zt_ew_f32", inp, None, x, 0, 1e-4, 0.0, n3, s)
+        L2 = self._denoise_stream(D1, [x], [x], wp, H, W, 3, 3)
+        if cache_fn is None:
+            wpH = wps = self._zeros(1, 3, H, W)
+        else:
+            wpH, wps = cache_fn(L2)
+        u = self._pack(16 if self.dt else 12, H * W, [wpH, wps, L2], H, W)
+        f = self._conv(CV(u, 0, 9), "enhance.in_conv.0", wp["enhance.in_conv.0.bias"], 64, 3, "relu", wd=wp)
+        for _ in range(3):
+            f = self._conv(f, "enhance.conv.0", wp["enhance.conv.0.bias"], 64, 3, "relu", aux=f, epi=3, wd=wp)
+        s2 = self._conv(f, "enhance.out_conv.0", wp["enhance.out_conv.0.bias"], 3, 3, "sigmoid_clamp", out_planar=True, wd=wp)
+        H2 = self._new(1, 3, H, W)
+        lib.call("zt_ew_f32", x, s2, H2, 2, 1e-4, 1.0, n3, s)
+        if cache_fn is None:
+            wpH = wps = H2
+        self.last_wp = (wpH, wps)
+        H5p = self._denoise_stream(D2, [wpH, wps, H2, s2], [H2, s2], wp, H, W, 12, 6)
         return H2, H5p[:, :3], H5p[:, 3:]
 
     # ------------------------------------------------------------------------------------------------ loss + backward

@@ -1,0 +1,115 @@
+"""Streaming inference: `InferStep`, the inference twin of `optim.TrainStep`.
+
+`Finetunemodel.forward` launches every kernel eagerly and repacks the nine weight tensors per frame; that form stays as the
+parity-pinned API of the reference.  `InferStep` runs the same model for frozen weights: the weights are prepared once per
+binding (device layouts, eval-mode BatchNorm folded into enhance.conv.0), the frame is enhanced by `Engine.forward_stream`, the
+two uint8 images the scripts write are made inside the step, and the steady-state frame is one hipGraph replay."""
+import torch
+
+
+class InferStep:
+    """One frame of the inference loop (reference predict.py:40-55) as a callable:
+
+        step = InferStep(model, use_graph=True, ingest_size=(1920, 1080))
+        H2, H3, s3 = step(frame, is_new_seq)      # the three tensors of Finetunemodel.forward
+        enh_u8, out_u8 = step.u8                  # uint8 [H,W,3] device tensors of H2 / H3 (truncating quantisation, predict.py:57-61)
+
+    `frame` is fp32 [1,3,H,W], or a decoded uint8 frame ([H0,W0,3] / [1,H0,W0,3]) which goes through the ingest kernels
+    (`ingest_size` = (W, H) it is resized to, None = keep).  The recurrent cache update (`model.update_H3`) is part of the step.
+
+    use_graph=False: eager launches of the streaming plan.  use_graph=True: the frame is copied into a static input buffer and
+    the recurrent cache lives in static buffers; new-sequence frames and the first steady-state frame run eagerly, the second
+    steady-state frame is captured into a hipGraph (RAFT's side stream becomes a parallel branch, as in `TrainStep`) and later
+    frames replay it.  A change of the frame shape captures again.
+
+    THE RETURNED TENSORS AND `step.u8` LIVE IN THE STEP'S (GRAPH'S) BUFFERS: they are valid until the next call; copy what must
+    survive it.  The model must not be moved, and `last_H3 / last_s3` not re-assigned by the caller, after the capture.
+
+    Weights are prepared again when a parameter or BatchNorm buffer changed (`_version` / `data_ptr()` of the tensors, e.g. after
+    `load_state_dict`); the prepared buffers keep their addresses, so a captured graph stays valid across a reload."""
+
+    def __init__(self, model, use_graph=True, ingest_size=(1920, 1080)):
+        self.model, self.use_graph, self.ingest_size = model, use_graph, ingest_size
+        self.graph, self.x, self.out, self.u8 = None, None, None, None
+        self.n_eager_steady, self.n_captures, self.n_prepares = 0, 0, 0
+        self._wp, self._wsig, self._bound = None, None, None
+
+    # ---- frozen weights -----------------------------------------------------------------------------------------------------
+    def _tensors(self):
+        m = self.model
+        bn = m.enhance.conv[1]
+        return [p for _, p in m._trainable()] + [bn.running_mean, bn.running_var]
+
+    def _prepare(self):
+        """-> (engine, RAFT plan) with the prepared weight table current"""
+        eng, rp = self.model._plan()
+        bound = (eng, eng.precision)              # the engine object itself: a replaced engine (model.to(), new precision) never compares equal
+        if self._bound is None or self._bound[0] is not eng or self._bound[1] != eng.precision:
+            # the model moved / changed precision: new buffers, and no graph holds the old ones
+            self._bound, self._wp, self._wsig, self.graph, self.n_eager_steady = bound, None, None, None, 0
+        sig = tuple((t.data_ptr(), t._version) for t in self._tensors())
+        if sig != self._wsig:
+            with torch.no_grad():
+                self._wp = eng.prepare_stream(self._wp)
+            self._wsig = sig
+            self.n_prepares += 1
+        return eng, rp
+
+    # ---- one frame ----------------------------------------------------------------------------------------------------------
+    def _load(self, frame, dev, out=None):
+        """frame -> fp32 [1,3,H,W] on the device (uint8 frames through `Ops.ingest_u8`, as `TrainStep._load`)"""
+        if frame.dtype == torch.uint8:
+            self.model._plan()
+            return self.model._ops.ingest_u8(frame.to(dev, non_blocking=True), out=out, size=self.ingest_size)
+        if out is None:
+            return frame.to(dev, non_blocking=True).detach().contiguous().float()
+        out.copy_(frame, non_blocking=True)
+        return out
+
+    def _body(self, eng, rp, x):
+        m = self.model
+        new = m.is_new_seq or m.last_H3 is None
+        cache_fn = None if new else (lambda L2: rp.update_cache(m.last_H3, m.last_s3, L2, m.of_scale))
+        H2, H3, s3 = eng.forward_stream(x, cache_fn, self._wp)
+        m.last_H3_wp, m.last_s3_wp = eng.last_wp
+        m.update_H3(H3, s3)
+        u8 = (eng.ops.quantize_u8(H2, 0), eng.ops.quantize_u8(H3, 0))
+        return (H2, H3, s3), u8
+
+    def __call__(self, frame, is_new_seq=False):
+        m = self.model
+        m.is_new_seq = bool(is_new_seq)
+        dev = m._trainable()[0][1].device
+        eng, rp = self._prepare()
+        with torch.no_grad():
+            if not self.use_graph:
+                self.out, self.u8 = self._body(eng, rp, self._load(frame, dev))
+                return self.out
+            if frame.dtype == torch.uint8:
+                Wi, Hi = self.ingest_size if self.ingest_size is not None else (frame.shape[-2], frame.shape[-3])
+                shape = (1, 3, Hi, Wi)
+            else:
+                shape = tuple(frame.shape)
+            if self.x is not None and tuple(self.x.shape) != shape:      # the captured launch sequence no longer applies
+                self.graph, self.n_eager_steady, self.x = None, 0, None
+            if self.x is None:
+                self.x = torch.empty(shape, dtype=torch.float32, device=dev)
+                m.enable_static_cache(shape)
+            self._load(frame, dev, out=self.x)
+            if is_new_seq or m.last_H3 is None or self.n_eager_steady < 1:
+                # eager: new-sequence frames, and the first steady-state frame (loads every kernel's code object and sizes the
+                # RAFT plan's buffers before anything is captured)
+                if not (is_new_seq or m.last_H3 is None):
+                    self.n_eager_steady += 1
+                self.out, self.u8 = self._body(eng, rp, self.x)
+                return self.out
+            if self.graph is None:
+                torch.cuda.synchronize(dev)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    self._gout = self._body(eng, rp, self.x)
+                self.graph = g
+                self.n_captures += 1
+            self.graph.replay()
+            self.out, self.u8 = self._gout
+            return self.out

@@ -591,6 +591,29 @@ class Ops:
         self._ev_end(tok)
         return out
 
+    def denoise_fused_bf16(self, srcs, refs, w1, b1, w2, b2, w3, b3, cout, out=None, want_res=False):
+        """Whole Denoise_1 / Denoise_2 forward + tail in one launch (zt_denoise_fused_bf16): srcs = 1 or 4 planar fp32 [1,3,H,W]
+        tensors (concatenated), refs = the planar fp32 tensors subtracted from ([x] or [H2, s2]); w1/w2/w3 bf16 device layouts
+        [9,48,8|16] / [9,48,48] / [1,16,48], fp32 biases.  -> out [1,cout,H,W] = clamp(cat(refs) - net(cat(srcs)), 1e-4, 1)
+        (and the residual net(cat(srcs)) when want_res)."""
+        assert len(srcs) in (1, 4) and len(refs) * 3 == cout and cout in (3, 6)
+        for t in list(srcs) + list(refs):
+            _f32c(t)
+            assert tuple(t.shape) == tuple(srcs[0].shape) and t.shape[0] == 1 and t.shape[1] == 3
+        assert w1.dtype == w2.dtype == w3.dtype == torch.bfloat16
+        assert tuple(w1.shape[:2]) == (9, 48) and w1.shape[2] in (8, 16) and w1.shape[2] >= 3 * len(srcs)
+        assert tuple(w2.shape) == (9, 48, 48) and tuple(w3.shape) == (1, 16, 48)
+        _, _, H, W = srcs[0].shape
+        dev = srcs[0].device
+        if out is None:
+            out = torch.empty((1, cout, H, W), dtype=torch.float32, device=dev)
+        assert tuple(out.shape) == (1, cout, H, W) and out.dtype == torch.float32 and out.is_contiguous()
+        res = torch.empty_like(out) if want_res else None
+        s = list(srcs) + [None] * (4 - len(srcs))
+        self.lib.call("zt_denoise_fused_bf16", s[0], s[1], s[2], s[3], len(srcs), refs[0], refs[1] if cout == 6 else None,
+                      w1, w1.shape[2], _f32c(b1), w2, _f32c(b2), w3, _f32c(b3), cout, out, res, H, W, self._s(out))
+        return (out, res) if want_res else out
+
     def conv_pair_bf16(self, xA, wA, bA, CoutA, KA, outA, xB, wB, bB, CoutB, KB, outB, act=None):
         """Two independent stride-1 'same' convolutions (square kernels KA / KB) over the same map in ONE launch
         (zt_conv2d_pair_nhwc_bf16): bf16 NHWC in and out, y = act(conv + bias)."""
