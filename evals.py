@@ -38,6 +38,8 @@ parser.add_argument("--precision", type=str, default=None, choices=["fp32", "bf1
                     help="model precision: fp32 = parity mode, bf16 = throughput mode; when not given, ZEROTIG_PRECISION if set, else fp32")
 parser.add_argument("--graph", type=int, default=0, choices=[0, 1],
                     help="1: drive the loop through InferStep (weights prepared once, steady-state frames replayed as one hipGraph)")
+parser.add_argument("--device_png", type=int, default=0, choices=[0, 1],
+                    help="1: the --save_images files are deflated on the device and written by a threaded writer (same pixels)")
 
 
 def main():
@@ -64,6 +66,7 @@ def main():
     if args.graph:
         import importlib
         step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080))
+    writer = utils.png_writer() if args.device_png else None
     with torch.no_grad():
         for i, (inp, img_name, img_path, last_img_path) in enumerate(queue):
             new_seq = i == 0 or utils.sequential_judgment(img_path[0], last_img_path[0])
@@ -106,11 +109,17 @@ def main():
                 save_dir = os.path.join(args.save, parts[-3] + "/" + parts[-2])
                 os.makedirs(save_dir, exist_ok=True)
                 name = img_name[0].split("/")[-1].split(".")[0]
-                Image.fromarray(utils.quantize_u8(output).cpu().numpy()).save(save_dir + "/" + name + "_denoise.png", "PNG")
-                Image.fromarray(utils.quantize_u8(enhance).cpu().numpy()).save(save_dir + "/" + name + "_enhance.png", "PNG")
+                imgs = [("_denoise.png", utils.quantize_u8(output)), ("_enhance.png", utils.quantize_u8(enhance))]
                 if args.hist_match:                                # evals.py:178-181: np.round(x * 255), written as RGB
-                    Image.fromarray(utils.quantize_u8(hm, round_half_even=True).cpu().numpy()).save(
-                        save_dir + "/" + name + "_denoise_hm.png", "PNG")
+                    imgs.append(("_denoise_hm.png", utils.quantize_u8(hm, round_half_even=True)))
+                if writer is None:
+                    for suffix, u8 in imgs:
+                        Image.fromarray(u8.cpu().numpy()).save(save_dir + "/" + name + suffix, "PNG")
+                else:
+                    writer.submit([(save_dir + "/" + name + suffix,) + tuple(utils.png_encode(u8)) + (u8.shape[0], u8.shape[1])
+                                   for suffix, u8 in imgs])
+    if writer is not None:
+        writer.close()
     with open(os.path.join(args.save, "Metrics.json"), "w") as fh:
         hm_on = bool(args.hist_match)
         lp_on = lpips_model is not None

@@ -296,6 +296,21 @@ int zt_resample_u8_hwc(const unsigned char* src, unsigned char* dst, int Hi, int
 int zt_u8hwc_to_planar_f32(const unsigned char* src, float* dst, int H, int W, const float* lut256, zt_stream_t stream);
 
 
+/* ---- result PNGs encoded on the device (zt_png.hip) ------------------------------------------------------------------
+ * predict.py:57-61, 101-104 (and evals.py's --save_images files): `Image.fromarray(u8).save(path, "PNG")`.  src: uint8 [H][W][3] (what
+ * zt_quantize_u8_hwc writes) -> out: a complete zlib stream (78 01, deflate blocks, big-endian Adler-32) of the Paeth-filtered
+ * scanlines, *nbytes (device scalar) = its length; the host frames it as IHDR / IDAT / IEND with CRC-32s.  Blocks of 8 rows, each
+ * one dynamic-Huffman block of literals with its own length-limited canonical code (no LZ77 matching), byte-aligned by an empty
+ * stored block.  Deterministic.  ws (16-byte aligned) / out (4-byte aligned): at least the sizes zt_png_sizes reports.
+ * zt_png_sizes: pure host query (no device work, no stream): workspace and worst-case stream size in bytes for an H x W frame.
+ * zt_png_code_lengths: the code construction alone: hist257 = counts of the 256 byte values + end-of-block -> len257 = code
+ * lengths (0 = symbol unused, at most 15, Kraft sum exactly 1; a lone symbol gets an unused one-bit sibling). */
+int zt_png_sizes(int H, int W, size_t* ws_bytes, size_t* out_bytes);
+int zt_png_encode_u8(const unsigned char* src, int H, int W, void* ws, size_t ws_bytes, unsigned char* out, size_t out_bytes,
+                     unsigned* nbytes, zt_stream_t stream);
+int zt_png_code_lengths(const unsigned* hist257, unsigned char* len257, zt_stream_t stream);
+
+
 /* ---- hardware self-test probes (zt_probe.hip): pin the test emulator's model of gfx950 instructions to the chip ----- */
 /* ds_read_b64_tr_b16 on a [16][64] image of 16-bit codes: out[lane*4+q]; bf16 MFMA 16x16x32: D[16][16] = A[16][32] B[32][16] */
 int zt_probe_tr16(const unsigned short* img, unsigned short* out, int col0, zt_stream_t stream);

@@ -3,7 +3,9 @@
 import argparse
 import logging
 import os
+import json
 import sys
+import time
 
 import numpy as np
 import torch
@@ -29,6 +31,11 @@ parser.add_argument("--precision", type=str, default=None, choices=["fp32", "bf1
 parser.add_argument("--graph", type=int, default=0, choices=[0, 1],
                     help="1: drive the loop through InferStep (weights prepared once, steady-state frames replayed as one hipGraph)")
 
+
+parser.add_argument("--device_png", type=int, default=0, choices=[0, 1],
+                    help="1: the result PNGs are deflated on the device and written by a threaded writer (same pixels, other file bytes)")
+parser.add_argument("--timing_json", type=str, default=None,
+                    help="write the loop's host-side time split (decode wait, step, copy wait, writer wait) to this file")
 
 def save_images(tensor):
     """predict.py:57-61: clip(x * 255, 0, 255).astype(uint8), HWC -- quantised and interleaved on the device (6 MB instead of
@@ -56,26 +63,71 @@ def main():
     step = None
     if args.graph:
         import importlib
-        step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080))
-    with torch.no_grad():
-        for i, (inp, img_name, img_path, last_img_path) in enumerate(queue):
-            new_seq = i == 0 or sequential_judgment(img_path[0], last_img_path[0])
-            if step is not None:                   # the two uint8 images are made inside the step; valid until the next call
-                step(inp, new_seq)
-                enh_u8, out_u8 = (t.cpu().numpy() for t in step.u8)
-            else:
-                model.is_new_seq = new_seq
-                enhance, output, illum = model(utils.ingest_frame(inp, dev))
-                enh_u8, out_u8 = save_images(enhance), save_images(output)
-            if "RLV" == args.dataset:
-                parts = img_path[0].split(os.sep)
-                save_dir = os.path.join(args.save, parts[-3], parts[-2])
-            else:
-                save_dir = os.path.join(args.save, os.path.basename(os.path.split(img_path[0])[0]))
-            os.makedirs(save_dir, exist_ok=True)
-            name = img_name[0].split("/")[-1].split(".")[0]
-            Image.fromarray(out_u8).save(save_dir + "/" + name + "_denoise.png", "PNG")
-            Image.fromarray(enh_u8).save(save_dir + "/" + name + "_enhance.png", "PNG")
+        step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080), png=bool(args.device_png))
+    writer = utils.png_writer() if args.device_png else None
+    clock = time.perf_counter
+    t = {"decode_wait": 0.0, "step": 0.0, "copy_wait": 0.0, "write": 0.0}
+    frames, t_first = 0, None
+    try:
+        with torch.no_grad():
+            it = iter(queue)
+            while True:
+                t0 = clock()
+                try:
+                    inp, img_name, img_path, last_img_path = next(it)
+                except StopIteration:
+                    break
+                t1 = clock()
+                t_first = t1 if t_first is None else t_first      # the first frame has been read
+                i, frames = frames, frames + 1
+                new_seq = i == 0 or sequential_judgment(img_path[0], last_img_path[0])
+                if step is not None:               # the two uint8 images are made inside the step; valid until the next call
+                    step(inp, new_seq)
+                    enh_dev, out_dev = step.u8
+                    if writer is not None:
+                        enh_png, out_png = step.png
+                else:
+                    model.is_new_seq = new_seq
+                    enhance, output, illum = model(utils.ingest_frame(inp, dev))
+                    enh_dev, out_dev = utils.quantize_u8(enhance), utils.quantize_u8(output)   # predict.py:57-61 save_images
+                    if writer is not None:
+                        enh_png, out_png = utils.png_encode(enh_dev), utils.png_encode(out_dev)
+                t2 = clock()
+                if writer is None:
+                    enh_u8, out_u8 = enh_dev.cpu().numpy(), out_dev.cpu().numpy()
+                t3 = clock()
+                if "RLV" == args.dataset:
+                    parts = img_path[0].split(os.sep)
+                    save_dir = os.path.join(args.save, parts[-3], parts[-2])
+                else:
+                    save_dir = os.path.join(args.save, os.path.basename(os.path.split(img_path[0])[0]))
+                os.makedirs(save_dir, exist_ok=True)
+                name = img_name[0].split("/")[-1].split(".")[0]
+                if writer is None:
+                    Image.fromarray(out_u8).save(save_dir + "/" + name + "_denoise.png", "PNG")
+                    Image.fromarray(enh_u8).save(save_dir + "/" + name + "_enhance.png", "PNG")
+                else:                              # the copies are ordered on the stream: the next step may overwrite the buffers
+                    H, W = int(out_dev.shape[0]), int(out_dev.shape[1])
+                    writer.submit([(save_dir + "/" + name + "_denoise.png", out_png[0], out_png[1], H, W),
+                                   (save_dir + "/" + name + "_enhance.png", enh_png[0], enh_png[1], H, W)])
+                t4 = clock()
+                t["decode_wait"] += t1 - t0
+                t["step"] += t2 - t1
+                t["copy_wait"] += t3 - t2
+                t["write"] += t4 - t3
+    finally:
+        if writer is not None:
+            writer.close()
+    if args.timing_json and frames:
+        t_end = clock()                            # the last file has been closed
+        if writer is not None:                     # submit = wait for the byte counts (the step) + wait for a free buffer
+            t["copy_wait"] += writer.wait_copy
+            t["writer_wait"] = writer.wait_writer
+            t["write"] -= writer.wait_copy + writer.wait_writer
+        per = {k + "_ms": 1e3 * v / frames for k, v in t.items()}
+        with open(args.timing_json, "w") as fh:
+            json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), device_png=args.device_png,
+                           graph=args.graph), fh)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""GPU box: what the device PNG encoder (zt_png.hip, `--device_png 1`) buys predict.py.  One MI355X, at most 16 CPUs.
+
+(a) encode cost: HIP-event median over --reps calls of `Ops.png_encode` alone at 1080p and 4K on the "enhanced" synthetic frame
+    (low-light frame 3 of zero-tig_amd/synth.py scaled to mean 0.4), the stream size, and the share of the HBM peak for the bytes
+    the encode touches (input once, filtered scanlines written once and read twice, the stream zeroed, packed, read and gathered).
+(b) end to end: predict.py --graph 1 --precision bf16 over --frames synthetic 1080p PNG inputs in a temporary directory, for
+      parent         a checkout of the parent commit (--parent DIR; skipped when not given), run against this tree's library
+      device_png_0   this tree, PIL on the loop's thread
+      device_png_1   this tree, device encoder + threaded writer
+    Frames per second from the first frame read to the last file closed (predict.py --timing_json, with the host-side split per
+    frame: decode wait, step, copy wait, writer wait), and -- the only figure a tree without --timing_json can give -- the
+    differential rate (frames - short) / (wall(frames) - wall(short)) of two whole-process runs, which cancels the start-up.
+
+This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
+ends the run.  Writes the JSON to --out and prints it as one line.
+Usage: python tools/bench_predict.py [--parent DIR] [--frames 64] [--short 16] [--out profiles/predict_png_1080p.json]"""
+import argparse
+import importlib
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PEAK_HBM_GBS = 8000.0
+
+
+# ---- child: the encode alone ----------------------------------------------------------------------------------------------------
+def encode_mode(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("zero-tig_amd.lib").get_lib()               # raises without a HIP device
+    ops = importlib.import_module("zero-tig_amd.ops").Ops(lib)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    out = {}
+    for size in a.sizes:
+        H, W = [int(v) for v in size.split("x")]
+        f = synth.lowlight_frame(3, H, W)[0].transpose(1, 2, 0).astype(np.float64)
+        u8 = torch.from_numpy(np.ascontiguousarray(np.clip(np.clip(f * (0.4 / f.mean()), 0, 1) * 255, 0, 255).astype(np.uint8))).cuda()
+        ws_bytes, cap = ops.png_sizes(H, W)
+        stream = torch.empty(cap, dtype=torch.uint8, device="cuda")
+        for _ in range(3):
+            _, n = ops.png_encode(u8, out=stream)
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ops.png_encode(u8, out=stream)
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        nbytes = int(n.item())
+        scan = H * (3 * W + 1)
+        touched = 3 * H * W + 3 * scan + 4 * nbytes
+        med = statistics.median(ms)
+        out[size] = {"encode_ms": round(med, 4), "encode_ms_min": round(min(ms), 4), "stream_bytes": nbytes, "raw_bytes": 3 * H * W,
+                     "bytes_touched": touched, "gbs": round(touched / med / 1e6, 1),
+                     "hbm_share": round(touched / med / 1e6 / PEAK_HBM_GBS, 4), "workspace_bytes": ws_bytes, "capacity_bytes": cap}
+        print("[bench_predict] encode %s %s" % (size, out[size]), file=sys.stderr, flush=True)
+    with open(a.json, "w") as fh:
+        json.dump(out, fh)
+
+
+# ---- driver ---------------------------------------------------------------------------------------------------------------------
+def _one_frame(args):
+    import numpy as np
+    from PIL import Image
+    sys.path.insert(0, ROOT)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    t, path = args
+    a = synth.lowlight_frame(t, 1080, 1920)
+    Image.fromarray((np.transpose(a[0], (1, 2, 0)) * 255.0 + 0.5).astype(np.uint8)).save(path, compress_level=1)
+    return path
+
+
+def make_clip(tmp, frames, short, distinct):
+    """RLV-layout inputs: `distinct` different synthetic frames written once and copied round-robin to `frames` consecutive names
+    (and the first `short` of them to a second tree); weights from synth.make_state(3)"""
+    import multiprocessing as mp
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    src = os.path.join(tmp, "distinct")
+    os.makedirs(src)
+    with mp.get_context("spawn").Pool(min(8, distinct)) as pool:
+        files = pool.map(_one_frame, [(t, os.path.join(src, "%d.png" % t)) for t in range(distinct)])
+    roots = {}
+    for name, n in (("long", frames), ("short", short)):
+        d = os.path.join(tmp, name, "RLV", "input", "S01", "low_light_10")
+        os.makedirs(d)
+        for i in range(n):
+            shutil.copyfile(files[i % distinct], os.path.join(d, "%05d.png" % (i + 1)))
+        open(os.path.join(tmp, name, "RLV", "test_list.txt"), "w").write("S01\n")
+        roots[name] = os.path.join(tmp, name, "RLV")
+    weights = os.path.join(tmp, "weights.pt")
+    torch.save({k: torch.from_numpy(np.array(v)) for k, v in synth.make_state(3).items()}, weights)
+    return roots, weights
+
+
+def gpu_step(cmd, limit, env=None, cwd=ROOT):
+    """one GPU child under its own time limit; a failure ends the whole run"""
+    t0 = time.perf_counter()
+    r = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=cwd, env=env, capture_output=True, text=True)
+    dt = time.perf_counter() - t0
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout[-3000:] + r.stderr[-3000:])
+        raise SystemExit("[bench_predict] step failed with status %d, stopping: %s" % (r.returncode, " ".join(cmd)))
+    return dt
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "encode"])
+    ap.add_argument("--json", type=str, default=None)
+    ap.add_argument("--sizes", type=str, nargs="+", default=["1080x1920", "2160x3840"])
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--parent", type=str, default=None, help="checkout of the parent commit (runs against this tree's library)")
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--short", type=int, default=16)
+    ap.add_argument("--distinct", type=int, default=8)
+    ap.add_argument("--step-timeout", type=int, default=300)
+    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "predict_png_1080p.json"))
+    a = ap.parse_args()
+    if a.mode == "encode":
+        return encode_mode(a)
+    out = {"what": "predict.py --graph 1 --precision bf16 over %d synthetic 1080p PNG inputs (%d distinct): frames per second from the "
+                   "first frame read to the last file closed (timing_json), the differential whole-process rate over %d and %d "
+                   "frames, and the host-side split per frame; encode = Ops.png_encode alone, HIP-event median of %d calls"
+                   % (a.frames, a.distinct, a.frames, a.short, a.reps),
+           "cpus": len(os.sched_getaffinity(0)), "peak_hbm_gbs": PEAK_HBM_GBS}
+    tmp = tempfile.mkdtemp(prefix="zt_bench_predict_")
+    try:
+        ej = os.path.join(tmp, "encode.json")
+        gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "encode", "--json", ej, "--reps", str(a.reps), "--sizes"] + a.sizes,
+                 a.step_timeout)
+        out["encode"] = json.load(open(ej))
+        roots, weights = make_clip(tmp, a.frames, a.short, a.distinct)
+        so = os.path.join(ROOT, "zero-tig_amd", "libzerotig_hip.so")
+        configs = ([("parent", a.parent, [])] if a.parent else []) + [("device_png_0", ROOT, ["--device_png", "0"]),
+                                                                      ("device_png_1", ROOT, ["--device_png", "1"])]
+        out["end_to_end"] = {}
+        for name, tree, extra in configs:
+            env = dict(os.environ, PYTHONPATH=tree, ZEROTIG_HIP_LIB=so)
+            row, wall = {}, {}
+            for which, n in (("short", a.short), ("long", a.frames)):
+                save = os.path.join(tmp, "out_%s_%s" % (name, which))
+                cmd = [sys.executable, "predict.py", "--dataset", "RLV", "--lowlight_images_path", roots[which], "--model_pretrain", weights,
+                       "--save", save, "--graph", "1", "--precision", "bf16"] + extra
+                tj = os.path.join(tmp, "timing_%s_%s.json" % (name, which))
+                if extra:
+                    cmd += ["--timing_json", tj]
+                wall[which] = gpu_step(cmd, a.step_timeout, env=env, cwd=tree)
+                written = sum(len(fs) for _, _, fs in os.walk(save))
+                assert written == 2 * n, (name, which, written)
+                if which == "long":
+                    row["output_bytes_per_frame"] = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(save) for f in fs) // n
+                    if extra:
+                        row["loop"] = json.load(open(tj))
+                shutil.rmtree(save)
+            row["wall_s"] = {k: round(v, 2) for k, v in wall.items()}
+            row["differential_fps"] = round((a.frames - a.short) / (wall["long"] - wall["short"]), 2)
+            out["end_to_end"][name] = row
+            print("[bench_predict] %s %s" % (name, row), file=sys.stderr, flush=True)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -9,6 +9,7 @@ import torch
 
 _ops_mod = importlib.import_module("zero-tig_amd.ops")
 _lib_mod = importlib.import_module("zero-tig_amd.lib")
+_png_mod = importlib.import_module("zero-tig_amd.pngwriter")
 _OPS = None
 
 
@@ -114,6 +115,31 @@ def quantize_u8(tensor, round_half_even=False):
     """[1,3,H,W] in [0,1] on the device -> uint8 [H,W,3] on the device: predict.py:57-61 `save_images` (truncation) or, with
     round_half_even, evals.py:83-84 `np.round(x * 255).astype(np.uint8)`."""
     return _ops().quantize_u8(_prep(tensor), 1 if round_half_even else 0)
+
+
+def png_encode(u8):
+    """uint8 [H,W,3] on the device -> (zlib stream buffer, int32 byte count), both on the device (`Ops.png_encode`): the payload
+    of the PNG predict.py:101-104 writes for it.  Asynchronous; `PngWriter.submit` takes the pair."""
+    return _ops().png_encode(u8.contiguous())
+
+
+def png_writer(**kwargs):
+    """The threaded file writer behind `--device_png 1` (zero-tig_amd/pngwriter.py)."""
+    return _png_mod.PngWriter(**kwargs)
+
+
+def png_bytes(u8, ops=None):
+    """uint8 [H,W,3] on the device -> the bytes of the PNG file predict.py:101-104 writes for it, deflated on the device
+    (`Ops.png_encode`); synchronous.  The pixels decode identically; the file bytes differ from PIL's (no LZ77 matching)."""
+    stream, n = (ops or _ops()).png_encode(u8.contiguous())
+    data = stream[:int(n.item())].cpu().numpy()
+    return b"".join(bytes(p) for p in _png_mod.png_frame(data, int(u8.shape[0]), int(u8.shape[1])))
+
+
+def save_png(u8, path, ops=None):
+    """`Image.fromarray(u8.cpu().numpy()).save(path, "PNG")` with the compression done on the device; synchronous."""
+    with open(path, "wb") as fh:
+        fh.write(png_bytes(u8, ops))
 
 
 def psnr(img, gt):

@@ -13,24 +13,28 @@ class InferStep:
         step = InferStep(model, use_graph=True, ingest_size=(1920, 1080))
         H2, H3, s3 = step(frame, is_new_seq)      # the three tensors of Finetunemodel.forward
         enh_u8, out_u8 = step.u8                  # uint8 [H,W,3] device tensors of H2 / H3 (truncating quantisation, predict.py:57-61)
+        enh_png, out_png = step.png               # png=True: (zlib stream, byte count) of each, as `Ops.png_encode` returns them
 
     `frame` is fp32 [1,3,H,W], or a decoded uint8 frame ([H0,W0,3] / [1,H0,W0,3]) which goes through the ingest kernels
     (`ingest_size` = (W, H) it is resized to, None = keep).  The recurrent cache update (`model.update_H3`) is part of the step.
+
+    png=True: both uint8 images are also deflated inside the step (and inside the captured graph) into the zlib streams of their
+    PNG files (predict.py:101-104); `pngwriter.PngWriter.submit` copies and writes them.
 
     use_graph=False: eager launches of the streaming plan.  use_graph=True: the frame is copied into a static input buffer and
     the recurrent cache lives in static buffers; new-sequence frames and the first steady-state frame run eagerly, the second
     steady-state frame is captured into a hipGraph (RAFT's side stream becomes a parallel branch, as in `TrainStep`) and later
     frames replay it.  A change of the frame shape captures again.
 
-    THE RETURNED TENSORS AND `step.u8` LIVE IN THE STEP'S (GRAPH'S) BUFFERS: they are valid until the next call; copy what must
+    THE RETURNED TENSORS, `step.u8` AND `step.png` LIVE IN THE STEP'S (GRAPH'S) BUFFERS: they are valid until the next call; copy what must
     survive it.  The model must not be moved, and `last_H3 / last_s3` not re-assigned by the caller, after the capture.
 
     Weights are prepared again when a parameter or BatchNorm buffer changed (`_version` / `data_ptr()` of the tensors, e.g. after
     `load_state_dict`); the prepared buffers keep their addresses, so a captured graph stays valid across a reload."""
 
-    def __init__(self, model, use_graph=True, ingest_size=(1920, 1080)):
-        self.model, self.use_graph, self.ingest_size = model, use_graph, ingest_size
-        self.graph, self.x, self.out, self.u8 = None, None, None, None
+    def __init__(self, model, use_graph=True, ingest_size=(1920, 1080), png=False):
+        self.model, self.use_graph, self.ingest_size, self.want_png = model, use_graph, ingest_size, png
+        self.graph, self.x, self.out, self.u8, self.png = None, None, None, None, None
         self.n_eager_steady, self.n_captures, self.n_prepares = 0, 0, 0
         self._wp, self._wsig, self._bound = None, None, None
 
@@ -74,7 +78,8 @@ class InferStep:
         m.last_H3_wp, m.last_s3_wp = eng.last_wp
         m.update_H3(H3, s3)
         u8 = (eng.ops.quantize_u8(H2, 0), eng.ops.quantize_u8(H3, 0))
-        return (H2, H3, s3), u8
+        png = tuple(eng.ops.png_encode(u) for u in u8) if self.want_png else None
+        return (H2, H3, s3), u8, png
 
     def __call__(self, frame, is_new_seq=False):
         m = self.model
@@ -83,7 +88,7 @@ class InferStep:
         eng, rp = self._prepare()
         with torch.no_grad():
             if not self.use_graph:
-                self.out, self.u8 = self._body(eng, rp, self._load(frame, dev))
+                self.out, self.u8, self.png = self._body(eng, rp, self._load(frame, dev))
                 return self.out
             if frame.dtype == torch.uint8:
                 Wi, Hi = self.ingest_size if self.ingest_size is not None else (frame.shape[-2], frame.shape[-3])
@@ -101,7 +106,7 @@ class InferStep:
                 # RAFT plan's buffers before anything is captured)
                 if not (is_new_seq or m.last_H3 is None):
                     self.n_eager_steady += 1
-                self.out, self.u8 = self._body(eng, rp, self.x)
+                self.out, self.u8, self.png = self._body(eng, rp, self.x)
                 return self.out
             if self.graph is None:
                 torch.cuda.synchronize(dev)
@@ -111,5 +116,5 @@ class InferStep:
                 self.graph = g
                 self.n_captures += 1
             self.graph.replay()
-            self.out, self.u8 = self._gout
+            self.out, self.u8, self.png = self._gout
             return self.out

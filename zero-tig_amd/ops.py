@@ -179,6 +179,39 @@ class Ops:
         self.lib.call("zt_quantize_u8_hwc", x, out, H, W, int(mode), self._s(x))
         return out
 
+    def png_sizes(self, H, W):
+        """-> (workspace bytes, worst-case stream bytes) of `png_encode` for an H x W frame (host query, no device work)"""
+        import ctypes
+        ws, cap = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self.lib.call("zt_png_sizes", int(H), int(W), ctypes.byref(ws), ctypes.byref(cap))
+        return int(ws.value), int(cap.value)
+
+    def png_encode(self, u8_hwc, out=None):
+        """uint8 [H,W,3] on the device -> (stream, nbytes): `stream` is a uint8 buffer of worst-case size whose first `nbytes`
+        (int32 device scalar, shape [1]) bytes are the zlib stream of the image's Paeth-filtered scanlines -- the IDAT payload of
+        the PNG predict.py:101-104 writes.  Nothing synchronises: read `nbytes` after the stream has run.  `out`: a buffer of at
+        least `png_sizes(H, W)[1]` bytes to write into."""
+        assert u8_hwc.dtype == torch.uint8 and u8_hwc.dim() == 3 and u8_hwc.shape[2] == 3 and u8_hwc.is_contiguous()
+        H, W = int(u8_hwc.shape[0]), int(u8_hwc.shape[1])
+        ws_bytes, cap = self.png_sizes(H, W)
+        dev = u8_hwc.device
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= cap and out.device == dev
+        nbytes = torch.empty(1, dtype=torch.int32, device=dev)
+        self.lib.call("zt_png_encode_u8", u8_hwc, H, W, ws, ws_bytes, out, out.numel(), nbytes, self._s(u8_hwc))
+        return out, nbytes
+
+    def png_code_lengths(self, hist):
+        """257-bin histogram (256 byte values + end-of-block; any integer tensor) -> uint8 [257] code lengths of the encoder's
+        length-limited canonical Huffman code (at most 15 bits, Kraft sum exactly 1, 0 for symbols that do not occur)."""
+        assert hist.numel() == 257
+        h = hist.to(torch.int32).contiguous()
+        out = torch.empty(257, dtype=torch.uint8, device=h.device)
+        self.lib.call("zt_png_code_lengths", h, out, self._s(h))
+        return out
+
     def ingest_u8(self, u8, out=None, size=(1920, 1080)):
         """Decoded frame, uint8 [H0,W0,3] (or [1,H0,W0,3]) on the device -> fp32 [1,3,H,W] in [0,1]: the reference loader's
         `im.resize(size)` (PIL BICUBIC, 8-bit two-pass; skipped when the frame already has that size, as PIL does) followed by
