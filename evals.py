@@ -38,8 +38,9 @@ parser.add_argument("--precision", type=str, default=None, choices=["fp32", "bf1
                     help="model precision: fp32 = parity mode, bf16 = throughput mode; when not given, ZEROTIG_PRECISION if set, else fp32")
 parser.add_argument("--graph", type=int, default=0, choices=[0, 1],
                     help="1: drive the loop through InferStep (weights prepared once, steady-state frames replayed as one hipGraph)")
-parser.add_argument("--device_png", type=int, default=0, choices=[0, 1],
-                    help="1: the --save_images files are deflated on the device and written by a threaded writer (same pixels)")
+parser.add_argument("--device_png", type=int, default=0, choices=[0, 1, 2],
+                    help="1: the --save_images files are deflated on the device and written by a threaded writer (same pixels); "
+                         "2: the same with run-length matches, for frames with flat areas (never larger than 1)")
 
 
 def main():
@@ -116,7 +117,7 @@ def main():
                     for suffix, u8 in imgs:
                         Image.fromarray(u8.cpu().numpy()).save(save_dir + "/" + name + suffix, "PNG")
                 else:
-                    writer.submit([(save_dir + "/" + name + suffix,) + tuple(utils.png_encode(u8)) + (u8.shape[0], u8.shape[1])
+                    writer.submit([(save_dir + "/" + name + suffix,) + tuple(utils.png_encode(u8, args.device_png)) + (u8.shape[0], u8.shape[1])
                                    for suffix, u8 in imgs])
     if writer is not None:
         writer.close()

@@ -302,12 +302,18 @@ int zt_u8hwc_to_planar_f32(const unsigned char* src, float* dst, int H, int W, c
  * scanlines, *nbytes (device scalar) = its length; the host frames it as IHDR / IDAT / IEND with CRC-32s.  Blocks of 8 rows, each
  * one dynamic-Huffman block of literals with its own length-limited canonical code (no LZ77 matching), byte-aligned by an empty
  * stored block.  Deterministic.  ws (16-byte aligned) / out (4-byte aligned): at least the sizes zt_png_sizes reports.
+ * zt_png_encode_u8_mode: mode 1 = that stream (zt_png_encode_u8 means mode 1); mode 2 = the same scanlines, blocks and framing, but a
+ * block whose bytes have runs is written with run-length matches (length 3..258, distance 1, never reaching across the block; 286
+ * literal/length codes, one distance code) where that is strictly shorter, and exactly as in mode 1 otherwise: never longer than
+ * mode 1, and the mode-1 bytes where no block has a run worth a match.  Any other mode is ZT_EINVAL.  Same sizes for both modes.
  * zt_png_sizes: pure host query (no device work, no stream): workspace and worst-case stream size in bytes for an H x W frame.
  * zt_png_code_lengths: the code construction alone: hist257 = counts of the 256 byte values + end-of-block -> len257 = code
  * lengths (0 = symbol unused, at most 15, Kraft sum exactly 1; a lone symbol gets an unused one-bit sibling). */
 int zt_png_sizes(int H, int W, size_t* ws_bytes, size_t* out_bytes);
 int zt_png_encode_u8(const unsigned char* src, int H, int W, void* ws, size_t ws_bytes, unsigned char* out, size_t out_bytes,
                      unsigned* nbytes, zt_stream_t stream);
+int zt_png_encode_u8_mode(const unsigned char* src, int H, int W, int mode, void* ws, size_t ws_bytes, unsigned char* out,
+                          size_t out_bytes, unsigned* nbytes, zt_stream_t stream);
 int zt_png_code_lengths(const unsigned* hist257, unsigned char* len257, zt_stream_t stream);
 
 

@@ -32,8 +32,9 @@ parser.add_argument("--graph", type=int, default=0, choices=[0, 1],
                     help="1: drive the loop through InferStep (weights prepared once, steady-state frames replayed as one hipGraph)")
 
 
-parser.add_argument("--device_png", type=int, default=0, choices=[0, 1],
-                    help="1: the result PNGs are deflated on the device and written by a threaded writer (same pixels, other file bytes)")
+parser.add_argument("--device_png", type=int, default=0, choices=[0, 1, 2],
+                    help="1: the result PNGs are deflated on the device and written by a threaded writer (same pixels, other file bytes); "
+                         "2: the same with run-length matches, for frames with flat areas (never larger than 1)")
 parser.add_argument("--timing_json", type=str, default=None,
                     help="write the loop's host-side time split (decode wait, step, copy wait, writer wait) to this file")
 
@@ -63,7 +64,7 @@ def main():
     step = None
     if args.graph:
         import importlib
-        step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080), png=bool(args.device_png))
+        step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080), png=args.device_png)
     writer = utils.png_writer() if args.device_png else None
     clock = time.perf_counter
     t = {"decode_wait": 0.0, "step": 0.0, "copy_wait": 0.0, "write": 0.0}
@@ -91,7 +92,7 @@ def main():
                     enhance, output, illum = model(utils.ingest_frame(inp, dev))
                     enh_dev, out_dev = utils.quantize_u8(enhance), utils.quantize_u8(output)   # predict.py:57-61 save_images
                     if writer is not None:
-                        enh_png, out_png = utils.png_encode(enh_dev), utils.png_encode(out_dev)
+                        enh_png, out_png = utils.png_encode(enh_dev, args.device_png), utils.png_encode(out_dev, args.device_png)
                 t2 = clock()
                 if writer is None:
                     enh_u8, out_u8 = enh_dev.cpu().numpy(), out_dev.cpu().numpy()

@@ -1,20 +1,25 @@
 #!/usr/bin/env python3
-"""GPU box: what the device PNG encoder (zt_png.hip, `--device_png 1`) buys predict.py.  One MI355X, at most 16 CPUs.
+"""GPU box: what the device PNG encoder (zt_png.hip, `--device_png 1` / `2`) buys predict.py.  One MI355X, at most 16 CPUs.
 
-(a) encode cost: HIP-event median over --reps calls of `Ops.png_encode` alone at 1080p and 4K on the "enhanced" synthetic frame
-    (low-light frame 3 of zero-tig_amd/synth.py scaled to mean 0.4), the stream size, and the share of the HBM peak for the bytes
-    the encode touches (input once, filtered scanlines written once and read twice, the stream zeroed, packed, read and gathered).
+(a) encode cost: HIP-event median over --reps calls of `Ops.png_encode` alone at 1080p and 4K, mode 1 and mode 2 in the same
+    process, on the "enhanced_noisy" synthetic frame (low-light frame 3 of zero-tig_amd/synth.py scaled to mean 0.4 plus sigma-4
+    noise) and on its letterboxed form (the top and bottom 138 / 1080 of the rows black): the stream size, and the share of the
+    HBM peak for the bytes the encode touches (input once, filtered scanlines written once and read twice -- three times in mode 2,
+    which walks them once more for the run histogram --, the stream zeroed, packed, read and gathered).
 (b) end to end: predict.py --graph 1 --precision bf16 over --frames synthetic 1080p PNG inputs in a temporary directory, for
       parent         a checkout of the parent commit (--parent DIR; skipped when not given), run against this tree's library
       device_png_0   this tree, PIL on the loop's thread
       device_png_1   this tree, device encoder + threaded writer
+      device_png_2   the same with the encoder's mode 2 (run-length matches)
     Frames per second from the first frame read to the last file closed (predict.py --timing_json, with the host-side split per
-    frame: decode wait, step, copy wait, writer wait), and -- the only figure a tree without --timing_json can give -- the
-    differential rate (frames - short) / (wall(frames) - wall(short)) of two whole-process runs, which cancels the start-up.
+    frame: decode wait, step, copy wait, writer wait) for each of --repeats runs over the --frames inputs, their median and their
+    spread (max - min), and -- the only figure a tree without --timing_json can give -- the differential rate
+    (frames - short) / (median wall(frames) - wall(short)) of whole-process runs, which cancels the start-up.
 
 This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
 ends the run.  Writes the JSON to --out and prints it as one line.
-Usage: python tools/bench_predict.py [--parent DIR] [--frames 64] [--short 16] [--out profiles/predict_png_1080p.json]"""
+Usage: python tools/bench_predict.py [--parent DIR] [--frames 64] [--short 16] [--out profiles/predict_png_1080p.json]
+       python tools/bench_predict.py --skip-encode --frames 256 --short 64 --settings 1 2 --out profiles/predict_png_1080p_256.json"""
 import argparse
 import importlib
 import json
@@ -42,28 +47,40 @@ def encode_mode(a):
     for size in a.sizes:
         H, W = [int(v) for v in size.split("x")]
         f = synth.lowlight_frame(3, H, W)[0].transpose(1, 2, 0).astype(np.float64)
-        u8 = torch.from_numpy(np.ascontiguousarray(np.clip(np.clip(f * (0.4 / f.mean()), 0, 1) * 255, 0, 255).astype(np.uint8))).cuda()
+        e = np.clip(f * (0.4 / f.mean()), 0, 1)
+        noisy = np.clip(np.round(e * 255 + np.random.default_rng(4).normal(0, 4, e.shape)), 0, 255).astype(np.uint8)
+        box = noisy.copy()
+        bar = H * 138 // 1080
+        box[:bar] = 0
+        box[H - bar:] = 0
         ws_bytes, cap = ops.png_sizes(H, W)
         stream = torch.empty(cap, dtype=torch.uint8, device="cuda")
-        for _ in range(3):
-            _, n = ops.png_encode(u8, out=stream)
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            ops.png_encode(u8, out=stream)
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        nbytes = int(n.item())
-        scan = H * (3 * W + 1)
-        touched = 3 * H * W + 3 * scan + 4 * nbytes
-        med = statistics.median(ms)
-        out[size] = {"encode_ms": round(med, 4), "encode_ms_min": round(min(ms), 4), "stream_bytes": nbytes, "raw_bytes": 3 * H * W,
-                     "bytes_touched": touched, "gbs": round(touched / med / 1e6, 1),
-                     "hbm_share": round(touched / med / 1e6 / PEAK_HBM_GBS, 4), "workspace_bytes": ws_bytes, "capacity_bytes": cap}
-        print("[bench_predict] encode %s %s" % (size, out[size]), file=sys.stderr, flush=True)
+        out[size] = {"workspace_bytes": ws_bytes, "capacity_bytes": cap, "raw_bytes": 3 * H * W}
+        for fname, arr in (("enhanced_noisy", noisy), ("letterbox", box)):
+            u8 = torch.from_numpy(np.ascontiguousarray(arr)).cuda()
+            row = {}
+            for mode in (1, 2):
+                for _ in range(3):
+                    _, n = ops.png_encode(u8, out=stream, mode=mode)
+                torch.cuda.synchronize()
+                ms = []
+                for _ in range(a.reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    ops.png_encode(u8, out=stream, mode=mode)
+                    e1.record()
+                    e1.synchronize()
+                    ms.append(e0.elapsed_time(e1))
+                nbytes = int(n.item())
+                scan = H * (3 * W + 1)
+                touched = 3 * H * W + (2 + mode) * scan + 4 * nbytes
+                med = statistics.median(ms)
+                row["mode_%d" % mode] = {"encode_ms": round(med, 4), "encode_ms_min": round(min(ms), 4), "stream_bytes": nbytes,
+                                         "bytes_touched": touched, "gbs": round(touched / med / 1e6, 1),
+                                         "hbm_share": round(touched / med / 1e6 / PEAK_HBM_GBS, 4)}
+            row["mode_2_over_mode_1_ms"] = round(row["mode_2"]["encode_ms"] / row["mode_1"]["encode_ms"], 3)
+            out[size][fname] = row
+            print("[bench_predict] encode %s %s %s" % (size, fname, row), file=sys.stderr, flush=True)
     with open(a.json, "w") as fh:
         json.dump(out, fh)
 
@@ -125,6 +142,10 @@ def main():
     ap.add_argument("--parent", type=str, default=None, help="checkout of the parent commit (runs against this tree's library)")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--short", type=int, default=16)
+    ap.add_argument("--settings", type=int, nargs="+", default=[0, 1, 2], choices=[0, 1, 2],
+                    help="the --device_png values of part (b); a longer clip (--frames 256 --short 64 --settings 1 2) narrows the spread")
+    ap.add_argument("--skip-encode", action="store_true", help="part (b) only")
+    ap.add_argument("--repeats", type=int, default=3, help="runs over the --frames inputs per setting (the spread between them is reported)")
     ap.add_argument("--distinct", type=int, default=8)
     ap.add_argument("--step-timeout", type=int, default=300)
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "predict_png_1080p.json"))
@@ -133,40 +154,49 @@ def main():
         return encode_mode(a)
     out = {"what": "predict.py --graph 1 --precision bf16 over %d synthetic 1080p PNG inputs (%d distinct): frames per second from the "
                    "first frame read to the last file closed (timing_json), the differential whole-process rate over %d and %d "
-                   "frames, and the host-side split per frame; encode = Ops.png_encode alone, HIP-event median of %d calls"
-                   % (a.frames, a.distinct, a.frames, a.short, a.reps),
+                   "frames, and the host-side split per frame, %d runs per setting; encode = Ops.png_encode alone, mode 1 and 2, "
+                   "HIP-event median of %d calls" % (a.frames, a.distinct, a.frames, a.short, a.repeats, a.reps),
            "cpus": len(os.sched_getaffinity(0)), "peak_hbm_gbs": PEAK_HBM_GBS}
     tmp = tempfile.mkdtemp(prefix="zt_bench_predict_")
     try:
-        ej = os.path.join(tmp, "encode.json")
-        gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "encode", "--json", ej, "--reps", str(a.reps), "--sizes"] + a.sizes,
-                 a.step_timeout)
-        out["encode"] = json.load(open(ej))
+        if not a.skip_encode:
+            ej = os.path.join(tmp, "encode.json")
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "encode", "--json", ej, "--reps", str(a.reps), "--sizes"]
+                     + a.sizes, a.step_timeout)
+            out["encode"] = json.load(open(ej))
         roots, weights = make_clip(tmp, a.frames, a.short, a.distinct)
         so = os.path.join(ROOT, "zero-tig_amd", "libzerotig_hip.so")
-        configs = ([("parent", a.parent, [])] if a.parent else []) + [("device_png_0", ROOT, ["--device_png", "0"]),
-                                                                      ("device_png_1", ROOT, ["--device_png", "1"])]
+        configs = ([("parent", a.parent, [])] if a.parent else []) + [("device_png_%d" % v, ROOT, ["--device_png", str(v)])
+                                                                      for v in a.settings]
         out["end_to_end"] = {}
         for name, tree, extra in configs:
             env = dict(os.environ, PYTHONPATH=tree, ZEROTIG_HIP_LIB=so)
-            row, wall = {}, {}
-            for which, n in (("short", a.short), ("long", a.frames)):
-                save = os.path.join(tmp, "out_%s_%s" % (name, which))
-                cmd = [sys.executable, "predict.py", "--dataset", "RLV", "--lowlight_images_path", roots[which], "--model_pretrain", weights,
-                       "--save", save, "--graph", "1", "--precision", "bf16"] + extra
-                tj = os.path.join(tmp, "timing_%s_%s.json" % (name, which))
-                if extra:
-                    cmd += ["--timing_json", tj]
-                wall[which] = gpu_step(cmd, a.step_timeout, env=env, cwd=tree)
-                written = sum(len(fs) for _, _, fs in os.walk(save))
-                assert written == 2 * n, (name, which, written)
-                if which == "long":
-                    row["output_bytes_per_frame"] = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(save) for f in fs) // n
+            row, wall, loops = {}, {"short": [], "long": []}, []
+            for which, n, times in (("short", a.short, 1), ("long", a.frames, a.repeats)):
+                for _ in range(times):
+                    save = os.path.join(tmp, "out_%s_%s" % (name, which))
+                    cmd = [sys.executable, "predict.py", "--dataset", "RLV", "--lowlight_images_path", roots[which], "--model_pretrain",
+                           weights, "--save", save, "--graph", "1", "--precision", "bf16"] + extra
+                    tj = os.path.join(tmp, "timing_%s_%s.json" % (name, which))
                     if extra:
-                        row["loop"] = json.load(open(tj))
-                shutil.rmtree(save)
-            row["wall_s"] = {k: round(v, 2) for k, v in wall.items()}
-            row["differential_fps"] = round((a.frames - a.short) / (wall["long"] - wall["short"]), 2)
+                        cmd += ["--timing_json", tj]
+                    wall[which].append(gpu_step(cmd, a.step_timeout, env=env, cwd=tree))
+                    written = sum(len(fs) for _, _, fs in os.walk(save))
+                    assert written == 2 * n, (name, which, written)
+                    if which == "long":
+                        row["output_bytes_per_frame"] = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(save) for f in fs) // n
+                        if extra:
+                            loops.append(json.load(open(tj)))
+                    shutil.rmtree(save)
+                    print("[bench_predict] %s %s %.1f s" % (name, which, wall[which][-1]), file=sys.stderr, flush=True)
+            if loops:
+                fps = [l["fps"] for l in loops]
+                row["loop"] = sorted(loops, key=lambda l: l["fps"])[len(loops) // 2]          # the median run's split
+                row["fps_runs"] = [round(v, 2) for v in fps]
+                row["fps_median"] = round(statistics.median(fps), 2)
+                row["fps_spread"] = round(max(fps) - min(fps), 2)
+            row["wall_s"] = {k: [round(v, 2) for v in vs] for k, vs in wall.items()}
+            row["differential_fps"] = round((a.frames - a.short) / (statistics.median(wall["long"]) - wall["short"][0]), 2)
             out["end_to_end"][name] = row
             print("[bench_predict] %s %s" % (name, row), file=sys.stderr, flush=True)
     finally:

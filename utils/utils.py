@@ -117,29 +117,31 @@ def quantize_u8(tensor, round_half_even=False):
     return _ops().quantize_u8(_prep(tensor), 1 if round_half_even else 0)
 
 
-def png_encode(u8):
+def png_encode(u8, mode=1):
     """uint8 [H,W,3] on the device -> (zlib stream buffer, int32 byte count), both on the device (`Ops.png_encode`): the payload
-    of the PNG predict.py:101-104 writes for it.  Asynchronous; `PngWriter.submit` takes the pair."""
-    return _ops().png_encode(u8.contiguous())
+    of the PNG predict.py:101-104 writes for it.  Asynchronous; `PngWriter.submit` takes the pair.  mode 2 (`--device_png 2`):
+    run-length matches where a block of 8 rows has runs of equal filtered bytes; never longer than mode 1."""
+    return _ops().png_encode(u8.contiguous(), mode=mode)
 
 
 def png_writer(**kwargs):
-    """The threaded file writer behind `--device_png 1` (zero-tig_amd/pngwriter.py)."""
+    """The threaded file writer behind `--device_png 1` and `2` (zero-tig_amd/pngwriter.py)."""
     return _png_mod.PngWriter(**kwargs)
 
 
-def png_bytes(u8, ops=None):
+def png_bytes(u8, ops=None, mode=1):
     """uint8 [H,W,3] on the device -> the bytes of the PNG file predict.py:101-104 writes for it, deflated on the device
-    (`Ops.png_encode`); synchronous.  The pixels decode identically; the file bytes differ from PIL's (no LZ77 matching)."""
-    stream, n = (ops or _ops()).png_encode(u8.contiguous())
+    (`Ops.png_encode`); synchronous.  The pixels decode identically; the file bytes differ from PIL's (mode 1: no matching at
+    all; mode 2: run-length matches only)."""
+    stream, n = (ops or _ops()).png_encode(u8.contiguous(), mode=mode)
     data = stream[:int(n.item())].cpu().numpy()
     return b"".join(bytes(p) for p in _png_mod.png_frame(data, int(u8.shape[0]), int(u8.shape[1])))
 
 
-def save_png(u8, path, ops=None):
+def save_png(u8, path, ops=None, mode=1):
     """`Image.fromarray(u8.cpu().numpy()).save(path, "PNG")` with the compression done on the device; synchronous."""
     with open(path, "wb") as fh:
-        fh.write(png_bytes(u8, ops))
+        fh.write(png_bytes(u8, ops, mode))
 
 
 def psnr(img, gt):

@@ -19,7 +19,8 @@ class InferStep:
     (`ingest_size` = (W, H) it is resized to, None = keep).  The recurrent cache update (`model.update_H3`) is part of the step.
 
     png=True: both uint8 images are also deflated inside the step (and inside the captured graph) into the zlib streams of their
-    PNG files (predict.py:101-104); `pngwriter.PngWriter.submit` copies and writes them.
+    PNG files (predict.py:101-104); `pngwriter.PngWriter.submit` copies and writes them.  png=2: the same with the encoder's
+    mode 2 (run-length matches where a block has runs, `Ops.png_encode(.., mode=2)`); True means mode 1.
 
     use_graph=False: eager launches of the streaming plan.  use_graph=True: the frame is copied into a static input buffer and
     the recurrent cache lives in static buffers; new-sequence frames and the first steady-state frame run eagerly, the second
@@ -33,7 +34,8 @@ class InferStep:
     `load_state_dict`); the prepared buffers keep their addresses, so a captured graph stays valid across a reload."""
 
     def __init__(self, model, use_graph=True, ingest_size=(1920, 1080), png=False):
-        self.model, self.use_graph, self.ingest_size, self.want_png = model, use_graph, ingest_size, png
+        assert int(png) in (0, 1, 2), png
+        self.model, self.use_graph, self.ingest_size, self.want_png = model, use_graph, ingest_size, int(png)
         self.graph, self.x, self.out, self.u8, self.png = None, None, None, None, None
         self.n_eager_steady, self.n_captures, self.n_prepares = 0, 0, 0
         self._wp, self._wsig, self._bound = None, None, None
@@ -78,7 +80,7 @@ class InferStep:
         m.last_H3_wp, m.last_s3_wp = eng.last_wp
         m.update_H3(H3, s3)
         u8 = (eng.ops.quantize_u8(H2, 0), eng.ops.quantize_u8(H3, 0))
-        png = tuple(eng.ops.png_encode(u) for u in u8) if self.want_png else None
+        png = tuple(eng.ops.png_encode(u, mode=self.want_png) for u in u8) if self.want_png else None
         return (H2, H3, s3), u8, png
 
     def __call__(self, frame, is_new_seq=False):

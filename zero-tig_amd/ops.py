@@ -186,11 +186,13 @@ class Ops:
         self.lib.call("zt_png_sizes", int(H), int(W), ctypes.byref(ws), ctypes.byref(cap))
         return int(ws.value), int(cap.value)
 
-    def png_encode(self, u8_hwc, out=None):
+    def png_encode(self, u8_hwc, out=None, mode=1):
         """uint8 [H,W,3] on the device -> (stream, nbytes): `stream` is a uint8 buffer of worst-case size whose first `nbytes`
         (int32 device scalar, shape [1]) bytes are the zlib stream of the image's Paeth-filtered scanlines -- the IDAT payload of
         the PNG predict.py:101-104 writes.  Nothing synchronises: read `nbytes` after the stream has run.  `out`: a buffer of at
-        least `png_sizes(H, W)[1]` bytes to write into."""
+        least `png_sizes(H, W)[1]` bytes to write into.  mode 1: literal-only blocks; mode 2: a block with runs of equal
+        filtered bytes is written with run-length matches where that is shorter (never longer than mode 1; same sizes)."""
+        assert mode in (1, 2), mode
         assert u8_hwc.dtype == torch.uint8 and u8_hwc.dim() == 3 and u8_hwc.shape[2] == 3 and u8_hwc.is_contiguous()
         H, W = int(u8_hwc.shape[0]), int(u8_hwc.shape[1])
         ws_bytes, cap = self.png_sizes(H, W)
@@ -200,7 +202,7 @@ class Ops:
             out = torch.empty(cap, dtype=torch.uint8, device=dev)
         assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= cap and out.device == dev
         nbytes = torch.empty(1, dtype=torch.int32, device=dev)
-        self.lib.call("zt_png_encode_u8", u8_hwc, H, W, ws, ws_bytes, out, out.numel(), nbytes, self._s(u8_hwc))
+        self.lib.call("zt_png_encode_u8_mode", u8_hwc, H, W, int(mode), ws, ws_bytes, out, out.numel(), nbytes, self._s(u8_hwc))
         return out, nbytes
 
     def png_code_lengths(self, hist):
