@@ -42,6 +42,15 @@ int zt_box5_reflect_adj_f32(const float* src, float* dst, int C, int H, int W, f
 int zt_localvar_fwd_f32(const float* a, const float* b, float* D, float* V, int C, int H, int W, zt_stream_t stream);
 /* backward: xbar (+)= sign * (E - box0(E)/25), E = 2 D box0(gV)/25 */
 int zt_localvar_bwd_f32(const float* D, const float* gV, float* xbar, int C, int H, int W, float sign, int accumulate, zt_stream_t stream);
+/* both variance maps of the loss in one launch: (DA, VA) = localvar(a), (DX, VX) = localvar(b - a); same arithmetic as two
+   zt_localvar_fwd_f32 calls */
+int zt_localvar_fwd_pair_f32(const float* a, const float* b, float* DA, float* VA, float* DX, float* VX, int C, int H, int W, zt_stream_t stream);
+/* the variance term's backward in one launch, equal to zt_localvar_bwd_f32(DN, gV, dH3, -1, accumulate) followed by
+   zt_localvar_bwd_f32(DH2, gV, dH2x, +1, write) and zt_localvar_bwd_f32(DN, gV, dH2x, +1, accumulate) */
+int zt_localvar_bwd_pair_f32(const float* DN, const float* DH2, const float* gV, float* dH3, float* dH2x, int C, int H, int W, zt_stream_t stream);
+/* dst[C][H][W] = pd^T(g1 - box5_reflect^T(u1), g2 - box5_reflect^T(u2)) for half-resolution u1, u2, g1, g2 [C][H/2][W/2]: equal to
+   zt_box5_reflect_adj_f32(scale -1, accumulate) on g1 and g2 followed by zt_pair_down_adj_f32, without writing g1 / g2 back */
+int zt_half_bwd_f32(const float* u1, const float* u2, const float* g1, const float* g2, float* dst, int C, int H, int W, zt_stream_t stream);
 /* loss.py:99-136 TextureDifference: a, b planar [3][H][W] -> mask [H][W] in {0,1}; ratio (optional) = 2 s1 s2 / (s1^2+s2^2+1e-5) */
 int zt_texture_mask_f32(const float* a, const float* b, float* mask, float* ratio, int H, int W, zt_stream_t stream);
 /* loss.py:178-190 SmoothLoss.rgb2yCbCr over the flat memory (nelem = 3*H*W) */
@@ -105,6 +114,10 @@ int zt_bn_bwd_reduce(const void* dy, int dt, int lddy, const void* z, int ldz, c
                          const float* mean, const float* rstd, int HW, int C, int nblk, float* partial, zt_stream_t stream);
 int zt_partial_reduce_f32(const float* partial, int nblk, int stride, int n, float* out, int accumulate, float* out2,
                           zt_stream_t stream);
+/* terms[0..16] of the loss from the partials of zt_loss_s2_f32 (p1 [nb1][4]), zt_loss_half_f32 (p2 [nb2][10]) and zt_loss_full_f32
+   (p3 [nb3][3]) in one launch; every term is summed exactly as zt_partial_reduce_f32 sums a column */
+int zt_loss_terms_reduce_f32(const float* p1, int nb1, const float* p2, int nb2, const float* p3, int nb3, float* terms,
+                             zt_stream_t stream);
 /* one launch for a BatchNorm layer's backward sums: sums[0:2C] = column sums of partial [nblk][2][C]; dbeta += sums[0:C],
    dgamma += sums[C:2C] (torch BatchNorm2d backward, reference model.py:60-67 through autograd) */
 int zt_bn_bwd_sums_f32(const float* partial, int nblk, int C, float* dbeta, float* dgamma, float* sums, zt_stream_t stream);
@@ -161,6 +174,8 @@ int zt_add3_f32(const float* a, const float* b, const float* c, float* out, long
 int zt_plane_sums_f32(const float* x, int C, long long HW, int nblk, float* partial, zt_stream_t stream);
 /* loss.py:26-37: scal[0..2] = clamp(enhancement_factor,1,25), scal[3..5] = 0.7^-ef / ef */
 int zt_loss_scalars_f32(const float* partial, int nblk, long long HW, int is_WB, float* scal, zt_stream_t stream);
+/* the same scalars by one lane straight from global memory (slow; the tests' reference for zt_loss_scalars_f32) */
+int zt_loss_scalars_serial_f32(const float* partial, int nblk, long long HW, int is_WB, float* scal, zt_stream_t stream);
 /* loss.py:46-49 (700 MSE, 1000 MSE, 5 SmoothLoss, 1600 L_TV): partial[block][4] + direct d/ds2.  fast_exp: 1 = hardware exponential for
  * the bilateral weights (bf16 throughput mode), 0 = libm expf (fp32 parity mode) */
 int zt_loss_s2_f32(const float* L2, const float* s2, const float* Y, const float* scal, int H, int W, float* ds2, float* partial,

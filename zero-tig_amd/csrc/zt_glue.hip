@@ -151,6 +151,25 @@ __global__ void __launch_bounds__(256) clamp_sub6_bwd_kernel(const float* __rest
   for (int k = 6; k < ld; ++k) ZtIO<T>::st(d + k, 0.f);
 }
 
+// bf16, ld == 8, 16-byte aligned dr: the pixel's eight channels (two of them padding) leave as ONE 16-byte store instead of
+// eight 2-byte ones.  Same per-element expressions.
+__global__ void __launch_bounds__(256) clamp_sub6_bwd_bf16x8_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                                    const float* __restrict__ r, const float* __restrict__ gA,
+                                                                    const float* __restrict__ gB, zt_bf16* __restrict__ dr,
+                                                                    long long HW) {
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= HW) return;
+  float v[8];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float pa = A[c * HW + i] - r[c * HW + i], pb = B[c * HW + i] - r[(c + 3) * HW + i];
+    v[c] = in_clamp(pa, ZT_EPS, 1.f) ? -gA[c * HW + i] : 0.f;
+    v[c + 3] = in_clamp(pb, ZT_EPS, 1.f) ? -gB[c * HW + i] : 0.f;
+  }
+  v[6] = v[7] = 0.f;
+  zt_st8(dr + i * 8, v);
+}
+
 // Backward through H2 = clamp(x/s2), H11/H12 = clamp(L1x/s2x), (s21,s22) = pd(s2) and the Enhancer's
 // clamp(sigmoid) (model.py:79, 169-177): collects every gradient that reaches s2 and emits the Enhancer's
 // output-layer gradient  dO = ds2 * s2 (1 - s2) [s2 > 1e-4]  as NHWC (ld).
@@ -230,6 +249,106 @@ __global__ void __launch_bounds__(256) d1_bwd_prep_kernel(const float* __restric
     ZtIO<T>::st(dn12 + hp * ld + j, 0.f);
   }
 }
+
+// The two kernels above for bf16, ld == 8 and aligned buffers.  A thread still owns one 2 x 2 block, but each of its two rows
+// is read as one 8-byte pair -- the lanes of a wave then cover 128 consecutive full-resolution pixels of a row instead of every
+// other 4-byte word -- and each pixel leaves as one 16-byte store, the two pixels of a row as 32 contiguous bytes.
+// Per-element expressions are unchanged.
+__device__ __forceinline__ float2 ld2(const float* p) { return *reinterpret_cast<const float2*>(p); }
+
+__global__ void __launch_bounds__(256) post_enh_bwd_bf16x8_kernel(const float* __restrict__ x, const float* __restrict__ s2,
+                                                                  const float* __restrict__ L11, const float* __restrict__ L12,
+                                                                  const float* __restrict__ s21, const float* __restrict__ s22,
+                                                                  const float* __restrict__ dIn5, const float* __restrict__ dH2x,
+                                                                  const float* __restrict__ dIn3, const float* __restrict__ dIn4,
+                                                                  const float* __restrict__ ds2_direct, zt_bf16* __restrict__ dO,
+                                                                  float* __restrict__ ds2_total, int H, int W) {
+  const int h = H >> 1, w = W >> 1;
+  int hx = blockIdx.x * 64 + threadIdx.x, hy = blockIdx.y * 4 + threadIdx.y;
+  if (hx >= w || hy >= h) return;
+  const size_t HW = (size_t)H * W, hw = (size_t)h * w;
+  const size_t hp = (size_t)hy * w + hx;
+  const size_t p = (size_t)(2 * hy) * W + 2 * hx;
+  float out[2][2][8];                                            // [row][column][channel]
+#pragma unroll
+  for (int ry = 0; ry < 2; ++ry)
+#pragma unroll
+    for (int rx = 0; rx < 2; ++rx)
+#pragma unroll
+      for (int j = 3; j < 8; ++j) out[ry][rx][j] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    size_t ho = (size_t)c * hw + hp;
+    float a21 = s21[ho], a22 = s22[ho];
+    float q1 = L11[ho] / a21, q2 = L12[ho] / a22;
+    float g21 = dIn3[(9 + c) * hw + hp] + (in_clamp(q1, ZT_EPS, 1.f) ? dIn3[(6 + c) * hw + hp] * (-q1 / a21) : 0.f);
+    float g22 = dIn4[(9 + c) * hw + hp] + (in_clamp(q2, ZT_EPS, 1.f) ? dIn4[(6 + c) * hw + hp] * (-q2 / a22) : 0.f);
+    const float pdadj[2][2] = {{0.5f * g22, 0.5f * g21}, {0.5f * g21, 0.5f * g22}};
+#pragma unroll
+    for (int ry = 0; ry < 2; ++ry) {
+      const size_t pp = p + (size_t)ry * W, oo = (size_t)c * HW + pp;
+      const float2 sv = ld2(s2 + oo), xv = ld2(x + oo), d5h = ld2(dIn5 + (6 + c) * HW + pp), dhx = ld2(dH2x + oo);
+      const float2 dd = ld2(ds2_direct + oo), d5s = ld2(dIn5 + (9 + c) * HW + pp);
+      float gg[2];
+#pragma unroll
+      for (int rx = 0; rx < 2; ++rx) {
+        float s = rx ? sv.y : sv.x;
+        float q = (rx ? xv.y : xv.x) / s;
+        float gH2 = (rx ? d5h.y : d5h.x) + (rx ? dhx.y : dhx.x);
+        float g = (rx ? dd.y : dd.x) + (rx ? d5s.y : d5s.x) + pdadj[ry][rx] + (in_clamp(q, ZT_EPS, 1.f) ? gH2 * (-q / s) : 0.f);
+        gg[rx] = g;
+        out[ry][rx][c] = (s > ZT_EPS) ? g * s * (1.f - s) : 0.f;
+      }
+      if (ds2_total) *reinterpret_cast<float2*>(ds2_total + oo) = make_float2(gg[0], gg[1]);
+    }
+  }
+#pragma unroll
+  for (int ry = 0; ry < 2; ++ry)
+#pragma unroll
+    for (int rx = 0; rx < 2; ++rx) zt_st8(dO + (p + (size_t)ry * W + rx) * 8, out[ry][rx]);
+}
+
+__global__ void __launch_bounds__(256) d1_bwd_prep_bf16x8_kernel(const float* __restrict__ x, const float* __restrict__ n,
+                                                                 const float* __restrict__ dLp1, const float* __restrict__ dLp2,
+                                                                 const float* __restrict__ dden1, const float* __restrict__ dden2,
+                                                                 zt_bf16* __restrict__ dn, zt_bf16* __restrict__ dn11,
+                                                                 zt_bf16* __restrict__ dn12, int H, int W) {
+  const int h = H >> 1, w = W >> 1;
+  int hx = blockIdx.x * 64 + threadIdx.x, hy = blockIdx.y * 4 + threadIdx.y;
+  if (hx >= w || hy >= h) return;
+  const size_t HW = (size_t)H * W, hw = (size_t)h * w;
+  const size_t hp = (size_t)hy * w + hx;
+  const size_t p = (size_t)(2 * hy) * W + 2 * hx;
+  float out[2][2][8], o11[8], o12[8];
+#pragma unroll
+  for (int j = 3; j < 8; ++j) {
+    out[0][0][j] = out[0][1][j] = out[1][0][j] = out[1][1][j] = 0.f;
+    o11[j] = o12[j] = 0.f;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float g1 = dden1[c * hw + hp], g2 = dden2[c * hw + hp];
+    const float adj[2][2] = {{0.5f * g2, 0.5f * g1}, {0.5f * g1, 0.5f * g2}};
+#pragma unroll
+    for (int ry = 0; ry < 2; ++ry) {
+      const size_t oo = c * HW + p + (size_t)ry * W;
+      const float2 xv = ld2(x + oo), nv = ld2(n + oo);
+      float pre0 = xv.x - nv.x, pre1 = xv.y - nv.y;
+      out[ry][0][c] = in_clamp(pre0, ZT_EPS, 1.f) ? -adj[ry][0] : 0.f;
+      out[ry][1][c] = in_clamp(pre1, ZT_EPS, 1.f) ? -adj[ry][1] : 0.f;
+    }
+    o11[c] = -dLp1[c * hw + hp];
+    o12[c] = -dLp2[c * hw + hp];
+  }
+#pragma unroll
+  for (int ry = 0; ry < 2; ++ry)
+#pragma unroll
+    for (int rx = 0; rx < 2; ++rx) zt_st8(dn + (p + (size_t)ry * W + rx) * 8, out[ry][rx]);
+  zt_st8(dn11 + hp * 8, o11);
+  zt_st8(dn12 + hp * 8, o12);
+}
+
+inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // out = a + b (+ c)  element-wise on flat fp32 buffers
 __global__ void __launch_bounds__(256) add3_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -343,6 +462,11 @@ extern "C" int zt_clamp_sub6_f32(const float* A, const float* B, const float* r,
 extern "C" int zt_clamp_sub6_bwd(const float* A, const float* B, const float* r, const float* gA, const float* gB,
                                  void* dr, int dt, int ld, long long HW, hipStream_t stream) {
   ZT_REQUIRE(A && B && r && gA && gB && dr && ld >= 6);
+  if (dt != 0 && ld == 8 && aligned_to(dr, 16)) {
+    hipLaunchKernelGGL(clamp_sub6_bwd_bf16x8_kernel, dim3((unsigned)zt_cdivl(HW, 256)), dim3(256), 0, stream, A, B, r, gA, gB, (zt_bf16*)dr, HW);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+  }
   if (dt == 0) hipLaunchKernelGGL(clamp_sub6_bwd_kernel<float>, dim3((unsigned)zt_cdivl(HW, 256)), dim3(256), 0, stream, A, B, r, gA, gB, (float*)dr, ld, HW);
   else hipLaunchKernelGGL(clamp_sub6_bwd_kernel<zt_bf16>, dim3((unsigned)zt_cdivl(HW, 256)), dim3(256), 0, stream, A, B, r, gA, gB, (zt_bf16*)dr, ld, HW);
   ZT_LAUNCH_CHECK();
@@ -355,6 +479,14 @@ extern "C" int zt_post_enh_bwd(const float* x, const float* s2, const float* L11
                                int W, hipStream_t stream) {
   ZT_REQUIRE(x && s2 && L11 && L12 && s21 && s22 && dIn5 && dH2x && dIn3 && dIn4 && ds2_direct && dO && ld >= 3);
   ZT_REQUIRE(H % 2 == 0 && W % 2 == 0);
+  // the 8-byte pair loads need every full-resolution plane 8-byte aligned (W and H * W are even)
+  if (dt != 0 && ld == 8 && aligned_to(dO, 16) && aligned_to(x, 8) && aligned_to(s2, 8) && aligned_to(dIn5, 8) && aligned_to(dH2x, 8) &&
+      aligned_to(ds2_direct, 8) && aligned_to(ds2_total, 8)) {
+    hipLaunchKernelGGL(post_enh_bwd_bf16x8_kernel, grid_half(H, W), dim3(64, 4), 0, stream, x, s2, L11, L12, s21, s22, dIn5, dH2x,
+                       dIn3, dIn4, ds2_direct, (zt_bf16*)dO, ds2_total, H, W);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+  }
   if (dt == 0)
     hipLaunchKernelGGL(post_enh_bwd_kernel<float>, grid_half(H, W), dim3(64, 4), 0, stream, x, s2, L11, L12, s21, s22, dIn5, dH2x,
                        dIn3, dIn4, ds2_direct, (float*)dO, ld, ds2_total, H, W);
@@ -369,6 +501,12 @@ extern "C" int zt_d1_bwd_prep(const float* x, const float* n, const float* dLp1,
                               const float* dden2, void* dn, void* dn11, void* dn12, int dt, int ld, int H, int W,
                               hipStream_t stream) {
   ZT_REQUIRE(x && n && dLp1 && dLp2 && dden1 && dden2 && dn && dn11 && dn12 && ld >= 3 && H % 2 == 0 && W % 2 == 0);
+  if (dt != 0 && ld == 8 && aligned_to(dn, 16) && aligned_to(dn11, 16) && aligned_to(dn12, 16) && aligned_to(x, 8) && aligned_to(n, 8)) {
+    hipLaunchKernelGGL(d1_bwd_prep_bf16x8_kernel, grid_half(H, W), dim3(64, 4), 0, stream, x, n, dLp1, dLp2, dden1, dden2,
+                       (zt_bf16*)dn, (zt_bf16*)dn11, (zt_bf16*)dn12, H, W);
+    ZT_LAUNCH_CHECK();
+    return ZT_OK;
+  }
   if (dt == 0)
     hipLaunchKernelGGL(d1_bwd_prep_kernel<float>, grid_half(H, W), dim3(64, 4), 0, stream, x, n, dLp1, dLp2, dden1, dden2, (float*)dn,
                        (float*)dn11, (float*)dn12, ld, H, W);

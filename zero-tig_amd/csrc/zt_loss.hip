@@ -50,12 +50,8 @@ __global__ void __launch_bounds__(256) plane_sums_scalar_kernel(const float* __r
   }
 }
 
-// loss.py:26-37: enhancement_factor ef[3] and adjustment_ratio[3] -> scal[0..2], scal[3..5]
-__global__ void loss_scalars_kernel(const float* __restrict__ partial, int nblk, double HW, int is_WB, float* __restrict__ scal) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double s[3] = {0, 0, 0};
-  for (int b = 0; b < nblk; ++b)
-    for (int c = 0; c < 3; ++c) s[c] += (double)partial[b * 3 + c];
+// loss.py:26-37: enhancement_factor ef[3] and adjustment_ratio[3] -> scal[0..2], scal[3..5] from the channel sums s[3]
+__device__ __forceinline__ void loss_scalars_tail(const double (&s)[3], double HW, int is_WB, float* __restrict__ scal) {
   float ef[3];
   if (is_WB) {
     for (int c = 0; c < 3; ++c) ef[c] = 0.3f / ((float)(s[c] / HW) + 1e-9f);
@@ -68,6 +64,36 @@ __global__ void loss_scalars_kernel(const float* __restrict__ partial, int nblk,
     scal[c] = e;
     scal[3 + c] = powf(0.7f, -e) / e;
   }
+}
+
+// The partials are brought into LDS by the whole workgroup (coalesced), LSC_BLK rows at a time (the training step has at most
+// 256); one lane then adds them in block order in double precision, the summation a single lane used to do through nblk * 3
+// dependent global loads.
+constexpr int LSC_BLK = 256;
+__global__ void __launch_bounds__(256) loss_scalars_kernel(const float* __restrict__ partial, int nblk, double HW, int is_WB,
+                                                           float* __restrict__ scal) {
+  __shared__ float sp[LSC_BLK * 3];
+  double s[3] = {0, 0, 0};
+  for (int b0 = 0; b0 < nblk; b0 += LSC_BLK) {
+    const int nb = nblk - b0 < LSC_BLK ? nblk - b0 : LSC_BLK;
+    for (int i = threadIdx.x; i < nb * 3; i += 256) sp[i] = partial[(size_t)b0 * 3 + i];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int b = 0; b < nb; ++b)
+        for (int c = 0; c < 3; ++c) s[c] += (double)sp[b * 3 + c];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss_scalars_tail(s, HW, is_WB, scal);
+}
+
+// The same result by the plain definition, one lane reading global memory: the reference the tests hold the kernel above to.
+__global__ void loss_scalars_serial_kernel(const float* __restrict__ partial, int nblk, double HW, int is_WB,
+                                           float* __restrict__ scal) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double s[3] = {0, 0, 0};
+  for (int b = 0; b < nblk; ++b)
+    for (int c = 0; c < 3; ++c) s[c] += (double)partial[b * 3 + c];
+  loss_scalars_tail(s, HW, is_WB, scal);
 }
 
 constexpr int k_off_dy[12] = {1, 0, 1, 1, 2, 0, 2, 2, 1, 1, 2, 2};
@@ -301,7 +327,14 @@ extern "C" int zt_plane_sums_f32(const float* x, int C, long long HW, int nblk, 
 
 extern "C" int zt_loss_scalars_f32(const float* partial, int nblk, long long HW, int is_WB, float* scal, hipStream_t stream) {
   ZT_REQUIRE(partial && scal);
-  hipLaunchKernelGGL(loss_scalars_kernel, dim3(1), dim3(64), 0, stream, partial, nblk, (double)HW, is_WB, scal);
+  hipLaunchKernelGGL(loss_scalars_kernel, dim3(1), dim3(256), 0, stream, partial, nblk, (double)HW, is_WB, scal);
+  ZT_LAUNCH_CHECK();
+  return ZT_OK;
+}
+
+extern "C" int zt_loss_scalars_serial_f32(const float* partial, int nblk, long long HW, int is_WB, float* scal, hipStream_t stream) {
+  ZT_REQUIRE(partial && scal && nblk > 0 && HW > 0);
+  hipLaunchKernelGGL(loss_scalars_serial_kernel, dim3(1), dim3(64), 0, stream, partial, nblk, (double)HW, is_WB, scal);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }

@@ -253,13 +253,9 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict_
   }
 }
 
-// out[j] (+)= sum_b partial[b*stride + j]   (fp64 combine); optional second destination without accumulation.
-// One workgroup per output element: 256 threads stride over the partials, fixed-order LDS tree (deterministic).
-__global__ void __launch_bounds__(256) partial_reduce_kernel(const float* __restrict__ partial, int nblk, int stride, int n,
-                                                             float* __restrict__ out, int accumulate,
-                                                             float* __restrict__ out2) {
-  __shared__ double sh[256];
-  const int j = blockIdx.x;
+// sum_b partial[b*stride + j] in fp64: 256 threads stride over the partials, fixed-order LDS tree (deterministic).
+// Result valid in thread 0.
+__device__ __forceinline__ float column_sum(const float* __restrict__ partial, int nblk, int stride, int j, double* sh) {
   double s = 0.0;
   for (int b = threadIdx.x; b < nblk; b += 256) s += (double)partial[(size_t)b * stride + j];
   sh[threadIdx.x] = s;
@@ -268,11 +264,36 @@ __global__ void __launch_bounds__(256) partial_reduce_kernel(const float* __rest
     if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
     __syncthreads();
   }
+  return (float)sh[0];
+}
+
+// out[j] (+)= sum_b partial[b*stride + j]   (fp64 combine); optional second destination without accumulation.
+// One workgroup per output element.
+__global__ void __launch_bounds__(256) partial_reduce_kernel(const float* __restrict__ partial, int nblk, int stride, int n,
+                                                             float* __restrict__ out, int accumulate,
+                                                             float* __restrict__ out2) {
+  __shared__ double sh[256];
+  const int j = blockIdx.x;
+  const float v = column_sum(partial, nblk, stride, j, sh);
   if (threadIdx.x == 0) {
-    float v = (float)sh[0];
     if (out) out[j] = accumulate ? out[j] + v : v;
     if (out2) out2[j] = v;
   }
+}
+
+// out[i] = column sum of segment i's partials, one workgroup per output: several partial_reduce launches whose outputs are
+// consecutive, as one (the table travels by value like wgrad's ReduceTable).
+constexpr int ZT_MAXCOL = 17;
+struct ColumnTable {
+  const float* src[ZT_MAXCOL];                                  // first element of the column
+  int nblk[ZT_MAXCOL], stride[ZT_MAXCOL];
+};
+
+__global__ void __launch_bounds__(256) partial_reduce_table_kernel(ColumnTable t, float* __restrict__ out) {
+  __shared__ double sh[256];
+  const int i = blockIdx.x;
+  const float v = column_sum(t.src[i], t.nblk[i], t.stride[i], 0, sh);
+  if (threadIdx.x == 0) out[i] = v;
 }
 
 // BatchNorm backward: the three column sums one layer needs from its [nblk][2][C] partials in one launch --
@@ -594,6 +615,23 @@ extern "C" int zt_partial_reduce_f32(const float* partial, int nblk, int stride,
                                      float* out2, hipStream_t stream) {
   ZT_REQUIRE(partial && n > 0 && (out || out2));
   hipLaunchKernelGGL(partial_reduce_kernel, dim3(n), dim3(256), 0, stream, partial, nblk, stride, n, out, accumulate, out2);
+  ZT_LAUNCH_CHECK();
+  return ZT_OK;
+}
+
+extern "C" int zt_loss_terms_reduce_f32(const float* p1, int nb1, const float* p2, int nb2, const float* p3, int nb3, float* terms,
+                                        hipStream_t stream) {
+  ZT_REQUIRE(p1 && p2 && p3 && terms && nb1 >= 1 && nb2 >= 1 && nb3 >= 1);
+  // term order of zt_loss.hip: 0-3 <- p1[:, 0:4] | 4-11 <- p2[:, 0:8] | 12-13 <- p3[:, 0:2] | 14-15 <- p2[:, 8:10] | 16 <- p3[:, 2]
+  ColumnTable t;
+  for (int i = 0; i < ZT_MAXCOL; ++i) {
+    if (i < 4) { t.src[i] = p1 + i; t.nblk[i] = nb1; t.stride[i] = 4; }
+    else if (i < 12) { t.src[i] = p2 + (i - 4); t.nblk[i] = nb2; t.stride[i] = 10; }
+    else if (i < 14) { t.src[i] = p3 + (i - 12); t.nblk[i] = nb3; t.stride[i] = 3; }
+    else if (i < 16) { t.src[i] = p2 + 8 + (i - 14); t.nblk[i] = nb2; t.stride[i] = 10; }
+    else { t.src[i] = p3 + 2; t.nblk[i] = nb3; t.stride[i] = 3; }
+  }
+  hipLaunchKernelGGL(partial_reduce_table_kernel, dim3(ZT_MAXCOL), dim3(256), 0, stream, t, terms);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }

@@ -435,7 +435,6 @@ class Engine:
         nb1 = ((W + 63) // 64) * ((H + 3) // 4)
         p1 = self._new(nb1, 4)
         lib.call("zt_loss_s2_f32", v["L2"], v["s2"], Y, scal, H, W, ds2, p1, self.dt, s)
-        o.partial_reduce(p1, nb1, 4, 4, out=terms)
         # ---- half-resolution terms
         LM1, LM2 = o.box5_reflect(v["H3d1"]), o.box5_reflect(v["H3d2"])
         dLp1, dLp2, dden1, dden2 = (self._new(1, 3, h, w) for _ in range(4))
@@ -446,17 +445,13 @@ class Engine:
         lib.call("zt_loss_half_f32", v["Lq11"], v["Lq12"], v["Lp1"], v["Lp2"], v["den1"], v["den2"], v["H3p"], v["H4p"],
                  v["H11"], v["s21"], v["H12"], v["s22"], v["H3d1"], v["H3d2"], v["m_h"], LM1, LM2, dLp1, dLp2, dden1, dden2,
                  dH3p, dH4p, dH3d1, dH3d2, u1, u2, hw, p2, s)
-        lib.call("zt_partial_reduce_f32", p2, nb2, 10, 8, terms.data_ptr() + 16, 0, None, s)
-        lib.call("zt_partial_reduce_f32", p2.data_ptr() + 32, nb2, 10, 2, terms.data_ptr() + 56, 0, None, s)
         # ---- full-resolution terms
-        DH2, VH2 = o.localvar_fwd(v["H2"])
-        DN, VN = o.localvar_fwd(v["H3"], v["H2"])
+        DH2, VH2, DN, VN = o.localvar_fwd_pair(v["H2"], v["H3"])
         dH3b, ds3, gV = self._new(1, 3, H, W), self._new(1, 3, H, W), self._new(1, 3, H, W)
         nb3 = (3 * HW + 255) // 256
         p3 = self._new(nb3, 3)
         lib.call("zt_loss_full_f32", v["H2b"], v["H3b"], v["s2"], v["s3"], VH2, VN, dH3b, ds3, gV, 3 * HW, p3, s)
-        lib.call("zt_partial_reduce_f32", p3, nb3, 3, 2, terms.data_ptr() + 48, 0, None, s)
-        lib.call("zt_partial_reduce_f32", p3.data_ptr() + 8, nb3, 3, 1, terms.data_ptr() + 64, 0, None, s)
+        o.loss_terms_reduce(p1, nb1, p2, nb2, p3, nb3, terms)
         loss = self._new(1)
         o.partial_reduce(terms, 17, 1, 1, out=loss)
         g = dict(ds2=ds2, dLp1=dLp1, dLp2=dLp2, dden1=dden1, dden2=dden2, dH3p=dH3p, dH4p=dH4p, dH3d1=dH3d1, dH3d2=dH3d2,
@@ -476,14 +471,10 @@ class Engine:
         dH3p, dH4p, dH3d1, dH3d2, u1, u2 = t["dH3p"], t["dH4p"], t["dH3d1"], t["dH3d2"], t["u1"], t["u2"]
         DH2, DN, dH3b, ds3, gV = t["DH2"], t["DN"], t["dH3b"], t["ds3"], t["gV"]
         # ---- backward: into H3 / H2
-        o.box5_reflect_adj(u1, -1.0, out=dH3d1)
-        o.box5_reflect_adj(u2, -1.0, out=dH3d2)
-        dH3 = o.pair_down_adj(dH3d1, dH3d2, H, W)
+        dH3 = o.half_bwd(u1, u2, dH3d1, dH3d2, H, W)
         tmp = self._new(1, 3, H, W)
         o.blur21_adj(dH3b, out=dH3, tmp=tmp)
-        o.localvar_bwd(DN, gV, -1.0, out=dH3)
-        dH2x = o.localvar_bwd(DH2, gV, 1.0)
-        o.localvar_bwd(DN, gV, 1.0, out=dH2x)
+        dH2x = o.localvar_bwd_pair(DN, DH2, gV, dH3)
         # ---- through the three Denoise_2 invocations (model.py:179-192)
         dr5, dr3, dr4 = self._newa(1, H, W, 8), self._newa(1, h, w, 8), self._newa(1, h, w, 8)
         lib.call("zt_clamp_sub6_bwd", v["H2"], v["s2"], v["r5"], dH3, ds3, dr5, self.dt, 8, HW, s)

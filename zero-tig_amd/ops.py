@@ -156,6 +156,27 @@ class Ops:
         self.lib.call("zt_localvar_bwd_f32", D, gV, out, C, H, W, float(sign), int(acc), self._s(D))
         return out
 
+    def localvar_fwd_pair(self, a, b):
+        """(D, V) of localvar_fwd(a) and of localvar_fwd(b, a) in one launch -> DA, VA, DX, VX"""
+        _, C, H, W = a.shape
+        DA, VA, DX, VX = (torch.empty_like(a) for _ in range(4))
+        self.lib.call("zt_localvar_fwd_pair_f32", a, b, DA, VA, DX, VX, C, H, W, self._s(a))
+        return DA, VA, DX, VX
+
+    def localvar_bwd_pair(self, DN, DH2, gV, dH3):
+        """dH3 += localvar_bwd(DN, gV, -1); returns dH2x = localvar_bwd(DH2, gV, +1) + localvar_bwd(DN, gV, +1), in one launch"""
+        _, C, H, W = DN.shape
+        dH2x = torch.empty_like(DN)
+        self.lib.call("zt_localvar_bwd_pair_f32", DN, DH2, gV, dH3, dH2x, C, H, W, self._s(DN))
+        return dH2x
+
+    def half_bwd(self, u1, u2, g1, g2, H, W):
+        """pair_down_adj(g1 - box5_reflect_adj(u1), g2 - box5_reflect_adj(u2)) -> [1,C,H,W] in one launch; g1 / g2 stay as they are"""
+        C = u1.shape[1]
+        out = torch.empty((1, C, H, W), dtype=torch.float32, device=u1.device)
+        self.lib.call("zt_half_bwd_f32", u1, u2, g1, g2, out, C, H, W, self._s(u1))
+        return out
+
     def texture_mask(self, a, b, want_ratio=False):
         _, C, H, W = a.shape
         assert C == 3
@@ -455,6 +476,11 @@ class Ops:
         self.lib.call("zt_norm_apply_nhwc", x.ptr, _dt(x.t), x.ld, scale, shift, rp, ldr, o.ptr, o.ld, x.N, x.H * x.W, x.C,
                       int(inner_relu), int(outer_relu), self._s(x.t))
         return out
+
+    def loss_terms_reduce(self, p1, nb1, p2, nb2, p3, nb3, terms):
+        """terms[0:17] from the three partial buffers of the loss kernels (one launch for five partial_reduce calls)"""
+        self.lib.call("zt_loss_terms_reduce_f32", p1, nb1, p2, nb2, p3, nb3, terms, self._s(p1))
+        return terms
 
     def partial_reduce(self, part, nblk, stride, n, out=None, accumulate=False, out2=None):
         self.lib.call("zt_partial_reduce_f32", part, nblk, stride, n, out, int(accumulate), out2, self._s(part))
