@@ -1,5 +1,6 @@
-"""The fused / tiled kernels of the loss tail against the entry points they replace (bit for bit), and the rewritten
-5x5 stencils against the CPU oracle.  Back-end "emu" runs on the CPU, back-end "hip" (marked gpu) on the MI355X."""
+"""The fused / tiled kernels of the loss tail against the entry points they replace (bit for bit), the local variance
+against a float32 replay of its operation order on the host (bit for bit), and the rewritten 5x5 stencils against the CPU
+oracle.  Back-end "emu" runs on the CPU, back-end "hip" (marked gpu) on the MI355X."""
 import numpy as np
 import pytest
 import torch
@@ -36,6 +37,64 @@ def test_localvar_fwd_pair(backend, H, W):
     DH2, VH2, DN, VN = ops.localvar_fwd_pair(H2, H3)
     for got, ref in ((DH2, rDH2), (VH2, rVH2), (DN, rDN), (VN, rVN)):
         assert torch.equal(got, ref)
+
+
+def _box0(x):
+    """zero-padded 5x5 box sum in float32: row sums left to right, then column sums top to bottom"""
+    H, W = x.shape[-2:]
+    q = np.pad(x, [(0, 0)] * (x.ndim - 2) + [(2, 2), (2, 2)])
+    hs = (((q[..., 0:W] + q[..., 1:W + 1]) + q[..., 2:W + 2]) + q[..., 3:W + 3]) + q[..., 4:W + 4]
+    return (((hs[..., 0:H, :] + hs[..., 1:H + 1, :]) + hs[..., 2:H + 2, :]) + hs[..., 3:H + 3, :]) + hs[..., 4:H + 4, :]
+
+
+def _lv_fwd_host(a, b=None):
+    f25 = np.float32(25)
+    x = a if b is None else a - b
+    D = x - _box0(x) / f25
+    return D, _box0(D * D) / f25
+
+
+def _lv_bwd_host(D, gV, sign):
+    f25 = np.float32(25)
+    S = _box0(gV) / f25
+    E = np.float32(2) * D * S
+    return np.float32(sign) * (E - _box0(E) / f25)
+
+
+@pytest.mark.parametrize("H,W", LV_SHAPES)
+def test_localvar_host_replay(backend, H, W):
+    """The single and the pair entry points are instantiations of one kernel template, so the pair tests above compare a text
+    with itself; this numpy float32 replay of the documented operation order anchors the arithmetic, bit for bit."""
+    ops, dev, _ = backend
+    ta, tb, tD2, tgV, tacc = (rnd(120 + i, 1, 3, H, W) for i in range(5))
+    a, b, D2, gV, acc = (t.numpy() for t in (ta, tb, tD2, tgV, tacc))
+    assert a.dtype == np.float32
+
+    def same(got, ref):
+        assert ref.dtype == np.float32
+        assert np.array_equal(got.cpu().numpy(), ref)
+
+    rDa, rVa = _lv_fwd_host(a)
+    rDx, rVx = _lv_fwd_host(b, a)
+    da, db = ta.to(dev), tb.to(dev)
+    D, V = ops.localvar_fwd(da)
+    same(D, rDa), same(V, rVa)
+    D, V = ops.localvar_fwd(db, da)
+    same(D, rDx), same(V, rVx)
+    none, V = ops.localvar_fwd(da, want_D=False)                     # null D
+    assert none is None
+    same(V, rVa)
+    for got, ref in zip(ops.localvar_fwd_pair(da, db), (rDa, rVa, rDx, rVx)):
+        same(got, ref)
+
+    dD, dD2, dgV = torch.from_numpy(rDa).to(dev), tD2.to(dev), tgV.to(dev)
+    same(ops.localvar_bwd(dD, dgV, 1.0), _lv_bwd_host(rDa, gV, 1))
+    same(ops.localvar_bwd(dD2, dgV, -1.0), _lv_bwd_host(D2, gV, -1))
+    same(ops.localvar_bwd(dD2, dgV, -1.0, out=tacc.clone().to(dev)), acc + _lv_bwd_host(D2, gV, -1))
+    dH3 = tacc.clone().to(dev)
+    dH2x = ops.localvar_bwd_pair(dD2, dD, dgV, dH3)                  # DN = D2, DH2 = D
+    same(dH3, acc + _lv_bwd_host(D2, gV, -1))
+    same(dH2x, _lv_bwd_host(rDa, gV, 1) + _lv_bwd_host(D2, gV, 1))
 
 
 HALF_SHAPES = [(6, 7), (9, 70), (20, 28), (21, 133)]

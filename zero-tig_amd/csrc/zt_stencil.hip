@@ -144,54 +144,93 @@ __global__ void __launch_bounds__(256) blur_vert_fold_kernel(const float* __rest
   }
 }
 
-// ------------------------------------------------------------------------------------------------ 5x5 reflect mean
-// 64 x 16 tiles with the +-2 halo staged once in LDS (coalesced loads); the 25 taps per pixel then come from LDS in the same
-// dy, dx order as the per-pixel global gathers they replace, so results are bit-identical.
-constexpr int B5_TX = 64, B5_TY = 16, B5_PW = B5_TX + 4, B5_PH = B5_TY + 4;
+// ------------------------------------------------------------------------------------------------ 5x5 tiles
+// Every 5x5 kernel below works on a 64 x 16 output tile with a 64 x 4 block: the inputs are staged once in LDS with their
+// halo (coalesced loads) and the taps come from LDS, in the order of the per-pixel global gathers they replace.
+constexpr int TX = 64, TY = 16;
+constexpr int PW = TX + 4, PH = TY + 4;      // tile with the +-2 halo of one 5x5 window
+constexpr int XW = TX + 8, XH = TY + 8;      // tile with the +-4 halo of two stacked windows
 
-// REFLECT: the slot holds the reflect-padded value (forward stencils).  Otherwise the address is only clamped into the image:
-// the adjoint reads the tile for pixels at least three away from every border, whose 25 sources are all inside the image.
-template <bool REFLECT>
-__device__ __forceinline__ float b5_stage_value(const float* __restrict__ p, int gy, int gx, int H, int W) {
-  if (REFLECT) {
-    gy = zt_reflect(gy < H + 2 ? gy : H + 1, H);                 // slots past the reflected border are never used
-    gx = zt_reflect(gx < W + 2 ? gx : W + 1, W);
-  } else {
-    gy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy);
-    gx = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
-  }
-  return p[(size_t)gy * W + gx];
+inline dim3 tile_grid(int W, int H, int C) { return dim3(zt_cdiv(W, TX), zt_cdiv(H, TY), C); }
+
+__device__ __forceinline__ bool in_image(int gy, int gx, int H, int W) { return gy >= 0 && gy < H && gx >= 0 && gx < W; }
+
+// in-image offset of the reflect-padded pixel (slots past the reflected border are never used)
+__device__ __forceinline__ size_t reflect_at(int gy, int gx, int H, int W) {
+  return (size_t)zt_reflect(gy < H + 2 ? gy : H + 1, H) * W + zt_reflect(gx < W + 2 ? gx : W + 1, W);
 }
 
-template <bool REFLECT>
-__device__ __forceinline__ void b5_stage(const float* __restrict__ p, float (*t)[B5_PW], int x0, int y0, int H, int W, int tid) {
-  for (int i = tid; i < B5_PH * B5_PW; i += 256) {
-    const int ly = i / B5_PW, lx = i - ly * B5_PW;
-    t[ly][lx] = b5_stage_value<REFLECT>(p, y0 + ly - 2, x0 + lx - 2, H, W);
+// in-image offset of the nearest pixel: the reflect adjoints read the tile only for pixels at least three away from every
+// border, whose 25 sources are all inside the image
+__device__ __forceinline__ size_t clamp_at(int gy, int gx, int H, int W) {
+  gy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy);
+  gx = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+  return (size_t)gy * W + gx;
+}
+
+// t[k][ly][lx] = v[k] of load(gy, gx, v) over the tile at (x0, y0) with its +-HALO halo: (gy, gx) = (y0 + ly - HALO,
+// x0 + lx - HALO) may lie outside the image, the loader decides what such a slot holds
+template <int HALO, int K, typename F>
+__device__ __forceinline__ void tile_fill(float (*t)[TY + 2 * HALO][TX + 2 * HALO], int x0, int y0, F load) {
+  constexpr int TW = TX + 2 * HALO, TH = TY + 2 * HALO;
+  for (int i = threadIdx.y * 64 + threadIdx.x; i < TH * TW; i += 256) {
+    const int ly = i / TW, lx = i - ly * TW;
+    float v[K];
+    load(y0 + ly - HALO, x0 + lx - HALO, v);
+#pragma unroll
+    for (int k = 0; k < K; ++k) t[k][ly][lx] = v[k];
   }
 }
 
-__global__ void __launch_bounds__(256) box5_reflect_kernel(const float* __restrict__ src, float* __restrict__ dst, int C,
-                                                           int H, int W) {
-  __shared__ float t[B5_PH][B5_PW];
-  const int c = blockIdx.z;
-  const int x0 = blockIdx.x * B5_TX, y0 = blockIdx.y * B5_TY;
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  b5_stage<true>(src + (size_t)c * H * W, t, x0, y0, H, W, tid);
-  __syncthreads();
+// f(ly, lx, y, x) for the thread's pixels of the tile that lie inside the H x W image: column threadIdx.x, rows threadIdx.y + 4 j
+template <typename F>
+__device__ __forceinline__ void for_owned(int x0, int y0, int H, int W, F f) {
   const int lx = threadIdx.x, x = x0 + lx;
 #pragma unroll
-  for (int j = 0; j < B5_TY / 4; ++j) {
+  for (int j = 0; j < TY / 4; ++j) {
     const int ly = threadIdx.y + 4 * j, y = y0 + ly;
-    if (x < W && y < H) {
-      float acc = 0.f;
-#pragma unroll
-      for (int dy = 0; dy < 5; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 5; ++dx) acc += t[ly + dy][lx + dx];
-      dst[(size_t)c * H * W + (size_t)y * W + x] = acc / 25.f;
-    }
+    if (x < W && y < H) f(ly, lx, y, x);
   }
+}
+
+// The 5-tap sums of the separable boxes, left to right and top to bottom (the bit-exact tests replay this order).
+// dst[r][c] = sum_{dx < 5} src[r][c + dx], or of its square: ROWS x DW sums from rows of SW floats
+template <int ROWS, int SW, int DW, bool SQUARE>
+__device__ __forceinline__ void row_sums5(const float* src, float* dst) {
+  for (int i = threadIdx.y * 64 + threadIdx.x; i < ROWS * DW; i += 256) {
+    const int r = i / DW, c = i - r * DW;
+    float v[5];
+#pragma unroll
+    for (int dx = 0; dx < 5; ++dx) {
+      const float s = src[r * SW + c + dx];
+      v[dx] = SQUARE ? s * s : s;
+    }
+    dst[r * DW + c] = (((v[0] + v[1]) + v[2]) + v[3]) + v[4];
+  }
+}
+
+template <int LD>
+__device__ __forceinline__ float col_sum5(const float* p) {
+  return (((p[0] + p[LD]) + p[2 * LD]) + p[3 * LD]) + p[4 * LD];
+}
+
+// ------------------------------------------------------------------------------------------------ 5x5 reflect mean
+__global__ void __launch_bounds__(256) box5_reflect_kernel(const float* __restrict__ src, float* __restrict__ dst, int C,
+                                                           int H, int W) {
+  __shared__ float t[PH][PW];
+  const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+  const size_t plane = (size_t)blockIdx.z * H * W;
+  const float* p = src + plane;
+  tile_fill<2, 1>(&t, x0, y0, [&](int gy, int gx, float (&v)[1]) { v[0] = p[reflect_at(gy, gx, H, W)]; });
+  __syncthreads();
+  for_owned(x0, y0, H, W, [&](int ly, int lx, int y, int x) {
+    float acc = 0.f;
+#pragma unroll
+    for (int dy = 0; dy < 5; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 5; ++dx) acc += t[ly + dy][lx + dx];
+    dst[plane + (size_t)y * W + x] = acc / 25.f;
+  });
 }
 
 __device__ __forceinline__ int fold_sources(int k, int n, int* u) {
@@ -205,7 +244,7 @@ __device__ __forceinline__ int fold_sources(int k, int n, int* u) {
 // adjoint(box5_reflect)(src) at (y, x), before the /25: pixels at least three away from every border have one fold source per
 // axis and all 25 taps inside the image -- they read the staged tile t (t[ly + 2][lx + 2] is the pixel itself); the others
 // gather from global memory with the folds.  Same dy, dx order on both paths.
-__device__ __forceinline__ float b5_adj_sum(const float* __restrict__ p, const float (*t)[B5_PW], int ly, int lx, int y, int x,
+__device__ __forceinline__ float b5_adj_sum(const float* __restrict__ p, const float (*t)[PW], int ly, int lx, int y, int x,
                                             int H, int W) {
   float acc = 0.f;
   if (y >= 3 && y < H - 3 && x >= 3 && x < W - 3) {
@@ -233,24 +272,17 @@ __device__ __forceinline__ float b5_adj_sum(const float* __restrict__ p, const f
 // dst = scale_out * adjoint(box5_reflect)(src)   (accumulate: dst += ...)
 __global__ void __launch_bounds__(256) box5_reflect_adj_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                                int C, int H, int W, float scale, int accumulate) {
-  __shared__ float t[B5_PH][B5_PW];
-  const int c = blockIdx.z;
-  const int x0 = blockIdx.x * B5_TX, y0 = blockIdx.y * B5_TY;
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  const float* p = src + (size_t)c * H * W;
-  b5_stage<false>(p, t, x0, y0, H, W, tid);
+  __shared__ float t[PH][PW];
+  const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+  const size_t plane = (size_t)blockIdx.z * H * W;
+  const float* p = src + plane;
+  tile_fill<2, 1>(&t, x0, y0, [&](int gy, int gx, float (&v)[1]) { v[0] = p[clamp_at(gy, gx, H, W)]; });
   __syncthreads();
-  const int lx = threadIdx.x, x = x0 + lx;
-#pragma unroll
-  for (int j = 0; j < B5_TY / 4; ++j) {
-    const int ly = threadIdx.y + 4 * j, y = y0 + ly;
-    if (x < W && y < H) {
-      float acc = b5_adj_sum(p, t, ly, lx, y, x, H, W);
-      acc = acc / 25.f * scale;
-      size_t o = (size_t)c * H * W + (size_t)y * W + x;
-      dst[o] = accumulate ? dst[o] + acc : acc;
-    }
-  }
+  for_owned(x0, y0, H, W, [&](int ly, int lx, int y, int x) {
+    const float acc = b5_adj_sum(p, t, ly, lx, y, x, H, W) / 25.f * scale;
+    const size_t o = plane + (size_t)y * W + x;
+    dst[o] = accumulate ? dst[o] + acc : acc;
+  });
 }
 
 // dst[C][H][W] = adjoint(pair_down)(g1 - adjoint(box5_reflect)(u1), g2 - adjoint(box5_reflect)(u2)) in one pass over the
@@ -260,302 +292,158 @@ __global__ void __launch_bounds__(256) box5_reflect_adj_kernel(const float* __re
 __global__ void __launch_bounds__(256) half_bwd_kernel(const float* __restrict__ u1, const float* __restrict__ u2,
                                                        const float* __restrict__ g1, const float* __restrict__ g2,
                                                        float* __restrict__ dst, int C, int H, int W, int h, int w) {
-  __shared__ float t1[B5_PH][B5_PW];
-  __shared__ float t2[B5_PH][B5_PW];
-  const int c = blockIdx.z;
-  const int x0 = blockIdx.x * B5_TX, y0 = blockIdx.y * B5_TY;
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  const float* p1 = u1 + (size_t)c * h * w;
-  const float* p2 = u2 + (size_t)c * h * w;
-  b5_stage<false>(p1, t1, x0, y0, h, w, tid);
-  b5_stage<false>(p2, t2, x0, y0, h, w, tid);
+  __shared__ float t[2][PH][PW];
+  const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+  const size_t hplane = (size_t)blockIdx.z * h * w;
+  const float* p1 = u1 + hplane;
+  const float* p2 = u2 + hplane;
+  tile_fill<2, 2>(t, x0, y0, [&](int gy, int gx, float (&v)[2]) {
+    const size_t o = clamp_at(gy, gx, h, w);
+    v[0] = p1[o];
+    v[1] = p2[o];
+  });
   __syncthreads();
-  const int lx = threadIdx.x, x = x0 + lx;
-  float* d = dst + (size_t)c * H * W;
+  float* d = dst + (size_t)blockIdx.z * H * W;
   const bool pair = (W & 1) == 0 && ((uintptr_t)dst & 7) == 0;   // even rows on an aligned base: the two pixels of a row are one 8-byte store
-#pragma unroll
-  for (int j = 0; j < B5_TY / 4; ++j) {
-    const int ly = threadIdx.y + 4 * j, y = y0 + ly;
-    if (x < w && y < h) {
-      const size_t ho = (size_t)c * h * w + (size_t)y * w + x;
-      const float a1 = b5_adj_sum(p1, t1, ly, lx, y, x, h, w) / 25.f * -1.f;
-      const float a2 = b5_adj_sum(p2, t2, ly, lx, y, x, h, w) / 25.f * -1.f;
-      const float v1 = 0.5f * (g1[ho] + a1), v2 = 0.5f * (g2[ho] + a2);
-      float* r0 = d + (size_t)(2 * y) * W + 2 * x;
-      float* r1 = r0 + W;
-      if (pair) {
-        *reinterpret_cast<float2*>(r0) = make_float2(v2, v1);
-        *reinterpret_cast<float2*>(r1) = make_float2(v1, v2);
-      } else {
-        r0[0] = v2; r0[1] = v1;
-        r1[0] = v1; r1[1] = v2;
-      }
-      const bool lastx = x == w - 1 && 2 * w < W, lasty = y == h - 1 && 2 * h < H;
-      if (lastx) r0[2] = r1[2] = 0.f;
-      if (lasty) {
-        r1[W] = r1[W + 1] = 0.f;
-        if (lastx) r1[W + 2] = 0.f;
-      }
+  for_owned(x0, y0, h, w, [&](int ly, int lx, int y, int x) {
+    const size_t ho = hplane + (size_t)y * w + x;
+    const float a1 = b5_adj_sum(p1, t[0], ly, lx, y, x, h, w) / 25.f * -1.f;
+    const float a2 = b5_adj_sum(p2, t[1], ly, lx, y, x, h, w) / 25.f * -1.f;
+    const float v1 = 0.5f * (g1[ho] + a1), v2 = 0.5f * (g2[ho] + a2);
+    float* r0 = d + (size_t)(2 * y) * W + 2 * x;
+    float* r1 = r0 + W;
+    if (pair) {
+      *reinterpret_cast<float2*>(r0) = make_float2(v2, v1);
+      *reinterpret_cast<float2*>(r1) = make_float2(v1, v2);
+    } else {
+      r0[0] = v2; r0[1] = v1;
+      r1[0] = v1; r1[1] = v2;
     }
-  }
+    const bool lastx = x == w - 1 && 2 * w < W, lasty = y == h - 1 && 2 * h < H;
+    if (lastx) r0[2] = r1[2] = 0.f;
+    if (lasty) {
+      r1[W] = r1[W + 1] = 0.f;
+      if (lastx) r1[W + 2] = 0.f;
+    }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ local variance (zero pad)
-// D = x - box0(x)/25 ; V = box0(D^2)/25     (x = a - b when b != nullptr)
-// 64 x 16 tiles, both 5x5 boxes separable in LDS (5 + 5 reads per output instead of 25, halo ratio 1.7 instead of 2.5): the
-// 32 x 8 / 25-tap form ran at ~0.9 TB/s of its 50-100 MB.
-#define LV_TX 64
-#define LV_TY 16
-constexpr int LV_XW = LV_TX + 8, LV_XH = LV_TY + 8;      // input tile with the +-4 halo of the two stacked boxes
-constexpr int LV_DW = LV_TX + 4, LV_DH = LV_TY + 4;      // intermediate (D / E) tile with the +-2 halo of the second box
-
-// hs[r][c] = sum_{dx < 5} xs[r][c + dx]  (LV_XH x LV_DW)
-__device__ __forceinline__ void lv_hsum_in(const float (*xs)[LV_XW], float (*hs)[LV_DW], int tid) {
-  for (int i = tid; i < LV_XH * LV_DW; i += 256) {
-    const int r = i / LV_DW, c = i - r * LV_DW;
-    hs[r][c] = (((xs[r][c] + xs[r][c + 1]) + xs[r][c + 2]) + xs[r][c + 3]) + xs[r][c + 4];
-  }
-}
-
+// Both 5x5 boxes are separable in LDS (5 + 5 reads per output instead of 25, halo ratio 1.7 instead of 2.5): the 32 x 8 /
+// 25-tap form ran at ~0.9 TB/s of its 50-100 MB.  One pipeline for K maps per tile: stage the +-4 tile (zero outside the
+// image), row sums, column sums + the pointwise step into the +-2 tile, row sums, column sums + the epilogue.  Per element:
+// row sums left to right, column sums top to bottom, then / 25.
+//
+// forward: D = x - box0(x)/25 ; V = box0(D^2)/25 for every map.
+//   K = 1: x = a, or a - b when b != nullptr; D0 may be null.
+//   K = 2: x0 = a, x1 = b - a -- localvar(a) and localvar(b - a) in one launch with a and b loaded once.
+template <int K>
 __global__ void __launch_bounds__(256) localvar_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                           float* __restrict__ D, float* __restrict__ V, int C, int H,
+                                                           float* __restrict__ D0, float* __restrict__ V0,
+                                                           float* __restrict__ D1, float* __restrict__ V1, int C, int H,
                                                            int W) {
-  __shared__ float xs[LV_XH][LV_XW];
-  __shared__ float hs[LV_XH][LV_DW];
-  __shared__ float ds[LV_DH][LV_DW];
-  __shared__ float h2[LV_DH][LV_TX];
-  const int c = blockIdx.z;
-  const int x0 = blockIdx.x * LV_TX, y0 = blockIdx.y * LV_TY;
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  const float* pa = a + (size_t)c * H * W;
-  const float* pb = b ? b + (size_t)c * H * W : nullptr;
-  for (int i = tid; i < LV_XH * LV_XW; i += 256) {
-    const int ly = i / LV_XW, lx = i - ly * LV_XW;
-    const int gy = y0 + ly - 4, gx = x0 + lx - 4;
-    const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    const size_t o = (size_t)(in ? gy : 0) * W + (in ? gx : 0);
-    float v = pa[o];
-    if (pb) v -= pb[o];
-    xs[ly][lx] = in ? v : 0.f;
-  }
-  __syncthreads();
-  lv_hsum_in(xs, hs, tid);
-  __syncthreads();
-  for (int i = tid; i < LV_DH * LV_DW; i += 256) {
-    const int r = i / LV_DW, cc = i - r * LV_DW;
-    const int gy = y0 + r - 2, gx = x0 + cc - 2;
-    float d = 0.f;
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-      const float sum = (((hs[r][cc] + hs[r + 1][cc]) + hs[r + 2][cc]) + hs[r + 3][cc]) + hs[r + 4][cc];
-      d = xs[r + 2][cc + 2] - sum / 25.f;
-      if (D && r >= 2 && r < LV_TY + 2 && cc >= 2 && cc < LV_TX + 2) D[(size_t)c * H * W + (size_t)gy * W + gx] = d;
-    }
-    ds[r][cc] = d;
-  }
-  __syncthreads();
-  for (int i = tid; i < LV_DH * LV_TX; i += 256) {
-    const int r = i / LV_TX, cc = i - r * LV_TX;
-    const float d0 = ds[r][cc], d1 = ds[r][cc + 1], d2 = ds[r][cc + 2], d3 = ds[r][cc + 3], d4 = ds[r][cc + 4];
-    h2[r][cc] = (((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3) + d4 * d4;
-  }
-  __syncthreads();
-  const int gx = x0 + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < LV_TY / 4; ++j) {
-    const int ly = threadIdx.y + 4 * j, gy = y0 + ly;
-    if (gx < W && gy < H) {
-      const float sum = (((h2[ly][threadIdx.x] + h2[ly + 1][threadIdx.x]) + h2[ly + 2][threadIdx.x]) + h2[ly + 3][threadIdx.x]) + h2[ly + 4][threadIdx.x];
-      V[(size_t)c * H * W + (size_t)gy * W + gx] = sum / 25.f;
-    }
-  }
-}
-
-// backward: xbar (+)= sign * (E - box0(E)/25), E = 2 D box0(gV)/25
-__global__ void __launch_bounds__(256) localvar_bwd_kernel(const float* __restrict__ D, const float* __restrict__ gV,
-                                                           float* __restrict__ xbar, int C, int H, int W, float sign,
-                                                           int accumulate) {
-  __shared__ float gs[LV_XH][LV_XW];
-  __shared__ float hs[LV_XH][LV_DW];
-  __shared__ float es[LV_DH][LV_DW];
-  __shared__ float h2[LV_DH][LV_TX];
-  const int c = blockIdx.z;
-  const int x0 = blockIdx.x * LV_TX, y0 = blockIdx.y * LV_TY;
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  const float* pg = gV + (size_t)c * H * W;
-  const float* pd = D + (size_t)c * H * W;
-  for (int i = tid; i < LV_XH * LV_XW; i += 256) {
-    const int ly = i / LV_XW, lx = i - ly * LV_XW;
-    const int gy = y0 + ly - 4, gx = x0 + lx - 4;
-    const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    const float v = pg[(size_t)(in ? gy : 0) * W + (in ? gx : 0)];
-    gs[ly][lx] = in ? v : 0.f;
-  }
-  __syncthreads();
-  lv_hsum_in(gs, hs, tid);
-  __syncthreads();
-  for (int i = tid; i < LV_DH * LV_DW; i += 256) {
-    const int r = i / LV_DW, cc = i - r * LV_DW;
-    const int gy = y0 + r - 2, gx = x0 + cc - 2;
-    float e = 0.f;
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-      const float sum = (((hs[r][cc] + hs[r + 1][cc]) + hs[r + 2][cc]) + hs[r + 3][cc]) + hs[r + 4][cc];
-      e = 2.f * pd[(size_t)gy * W + gx] * (sum / 25.f);
-    }
-    es[r][cc] = e;
-  }
-  __syncthreads();
-  for (int i = tid; i < LV_DH * LV_TX; i += 256) {
-    const int r = i / LV_TX, cc = i - r * LV_TX;
-    h2[r][cc] = (((es[r][cc] + es[r][cc + 1]) + es[r][cc + 2]) + es[r][cc + 3]) + es[r][cc + 4];
-  }
-  __syncthreads();
-  const int gx = x0 + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < LV_TY / 4; ++j) {
-    const int ly = threadIdx.y + 4 * j, gy = y0 + ly;
-    if (gx < W && gy < H) {
-      const float sum = (((h2[ly][threadIdx.x] + h2[ly + 1][threadIdx.x]) + h2[ly + 2][threadIdx.x]) + h2[ly + 3][threadIdx.x]) + h2[ly + 4][threadIdx.x];
-      const float v = sign * (es[ly + 2][threadIdx.x + 2] - sum / 25.f);
-      const size_t o = (size_t)c * H * W + (size_t)gy * W + gx;
-      xbar[o] = accumulate ? xbar[o] + v : v;
-    }
-  }
-}
-
-// (DA, VA) = localvar(a) and (DX, VX) = localvar(b - a) in one launch: the `a` tile is loaded once for both (two
-// localvar_fwd launches loaded it twice).  Per-element arithmetic is that of localvar_fwd_kernel; the second 5-tap row sums
-// reuse the LDS of the first.
-__global__ void __launch_bounds__(256) localvar_fwd_pair_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                                float* __restrict__ DA, float* __restrict__ VA,
-                                                                float* __restrict__ DX, float* __restrict__ VX, int C, int H,
-                                                                int W) {
-  __shared__ float xs[2][LV_XH][LV_XW];
-  __shared__ float hs[2][LV_XH][LV_DW];
-  __shared__ float ds[2][LV_DH][LV_DW];
-  const int c = blockIdx.z;
-  const int x0 = blockIdx.x * LV_TX, y0 = blockIdx.y * LV_TY;
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  const float* pa = a + (size_t)c * H * W;
-  const float* pb = b + (size_t)c * H * W;
-  float* const Dd[2] = {DA, DX};
-  float* const Vd[2] = {VA, VX};
-  for (int i = tid; i < LV_XH * LV_XW; i += 256) {
-    const int ly = i / LV_XW, lx = i - ly * LV_XW;
-    const int gy = y0 + ly - 4, gx = x0 + lx - 4;
-    const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    const size_t o = (size_t)(in ? gy : 0) * W + (in ? gx : 0);
+  __shared__ float xs[K][XH][XW];
+  __shared__ float hs[K][XH][PW];
+  __shared__ float ds[K][PH][PW];
+  const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+  const size_t plane = (size_t)blockIdx.z * H * W;
+  const float* pa = a + plane;
+  const float* pb = b ? b + plane : nullptr;
+  float* const Dd[2] = {D0, D1};
+  float* const Vd[2] = {V0, V1};
+  tile_fill<4, K>(xs, x0, y0, [&](int gy, int gx, float (&x)[K]) {
+    const bool in = in_image(gy, gx, H, W);
+    const size_t o = (size_t)(in ? gy : 0) * W + (in ? gx : 0);   // outside: load pixel (0, 0), then select 0
     const float va = pa[o];
-    float v = pb[o];
-    v -= va;
-    xs[0][ly][lx] = in ? va : 0.f;
-    xs[1][ly][lx] = in ? v : 0.f;
-  }
+    if constexpr (K == 1) {
+      float v = va;
+      if (pb) v -= pb[o];
+      x[0] = in ? v : 0.f;
+    } else {
+      float v = pb[o];
+      v -= va;
+      x[0] = in ? va : 0.f;
+      x[1] = in ? v : 0.f;
+    }
+  });
   __syncthreads();
-  lv_hsum_in(xs[0], hs[0], tid);
-  lv_hsum_in(xs[1], hs[1], tid);
-  __syncthreads();
-  for (int i = tid; i < LV_DH * LV_DW; i += 256) {
-    const int r = i / LV_DW, cc = i - r * LV_DW;
-    const int gy = y0 + r - 2, gx = x0 + cc - 2;
-    const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      float d = 0.f;
+  for (int k = 0; k < K; ++k) row_sums5<XH, XW, PW, false>(&xs[k][0][0], &hs[k][0][0]);
+  __syncthreads();
+  tile_fill<2, K>(ds, x0, y0, [&](int gy, int gx, float (&d)[K]) {
+    const int r = gy - y0 + 2, cc = gx - x0 + 2;
+    const bool in = in_image(gy, gx, H, W);
+    const bool owned = r >= 2 && r < TY + 2 && cc >= 2 && cc < TX + 2;   // D is written by the tile that owns the pixel
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      d[k] = 0.f;
       if (in) {
-        const float sum = (((hs[k][r][cc] + hs[k][r + 1][cc]) + hs[k][r + 2][cc]) + hs[k][r + 3][cc]) + hs[k][r + 4][cc];
-        d = xs[k][r + 2][cc + 2] - sum / 25.f;
-        if (r >= 2 && r < LV_TY + 2 && cc >= 2 && cc < LV_TX + 2) Dd[k][(size_t)c * H * W + (size_t)gy * W + gx] = d;
-      }
-      ds[k][r][cc] = d;
-    }
-  }
-  __syncthreads();
-  float (*h2)[LV_DH][LV_TX] = reinterpret_cast<float (*)[LV_DH][LV_TX]>(&hs[0][0][0]);   // hs is dead: 2 x 20 x 64 fits its 2 x 24 x 68
-  for (int i = tid; i < LV_DH * LV_TX; i += 256) {
-    const int r = i / LV_TX, cc = i - r * LV_TX;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const float d0 = ds[k][r][cc], d1 = ds[k][r][cc + 1], d2 = ds[k][r][cc + 2], d3 = ds[k][r][cc + 3], d4 = ds[k][r][cc + 4];
-      h2[k][r][cc] = (((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3) + d4 * d4;
-    }
-  }
-  __syncthreads();
-  const int tx = threadIdx.x, gx = x0 + tx;
-#pragma unroll
-  for (int j = 0; j < LV_TY / 4; ++j) {
-    const int ly = threadIdx.y + 4 * j, gy = y0 + ly;
-    if (gx < W && gy < H) {
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const float sum = (((h2[k][ly][tx] + h2[k][ly + 1][tx]) + h2[k][ly + 2][tx]) + h2[k][ly + 3][tx]) + h2[k][ly + 4][tx];
-        Vd[k][(size_t)c * H * W + (size_t)gy * W + gx] = sum / 25.f;
+        d[k] = xs[k][r + 2][cc + 2] - col_sum5<PW>(&hs[k][r][cc]) / 25.f;
+        if (Dd[k] && owned) Dd[k][plane + (size_t)gy * W + gx] = d[k];
       }
     }
-  }
+  });
+  __syncthreads();
+  float* const h2[2] = {&hs[0][0][0], &hs[K - 1][0][0]};             // hs is dead: 20 x 64 row sums per map fit its 24 x 68
+#pragma unroll
+  for (int k = 0; k < K; ++k) row_sums5<PH, PW, TX, true>(&ds[k][0][0], h2[k]);
+  __syncthreads();
+  for_owned(x0, y0, H, W, [&](int ly, int lx, int y, int x) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) Vd[k][plane + (size_t)y * W + x] = col_sum5<TX>(h2[k] + ly * TX + lx) / 25.f;
+  });
 }
 
-// The variance term's backward in one launch: with S = box0(gV)/25, E_N = 2 DN S and E_H = 2 DH2 S,
-//   dH3 += -(E_N - box0(E_N)/25)         dH2x = (E_H - box0(E_H)/25) + (E_N - box0(E_N)/25)
-// i.e. localvar_bwd(DN, gV, -1, accumulate), localvar_bwd(DH2, gV, +1), localvar_bwd(DN, gV, +1, accumulate) with gV staged
-// and S formed once, the DN stencil evaluated once and dH2x written once.  Same per-element arithmetic and order.
-__global__ void __launch_bounds__(256) localvar_bwd_pair_kernel(const float* __restrict__ DN, const float* __restrict__ DH2,
-                                                                const float* __restrict__ gV, float* __restrict__ dH3,
-                                                                float* __restrict__ dH2x, int C, int H, int W) {
-  __shared__ float gs[LV_XH][LV_XW];
-  __shared__ float hs[LV_XH][LV_DW];
-  __shared__ float en[LV_DH][LV_DW];
-  __shared__ float eh[LV_DH][LV_DW];
-  const int c = blockIdx.z;
-  const int x0 = blockIdx.x * LV_TX, y0 = blockIdx.y * LV_TY;
-  const int tid = threadIdx.y * 64 + threadIdx.x;
-  const float* pg = gV + (size_t)c * H * W;
-  const float* pn = DN + (size_t)c * H * W;
-  const float* ph = DH2 + (size_t)c * H * W;
-  for (int i = tid; i < LV_XH * LV_XW; i += 256) {
-    const int ly = i / LV_XW, lx = i - ly * LV_XW;
-    const int gy = y0 + ly - 4, gx = x0 + lx - 4;
-    const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    const float v = pg[(size_t)(in ? gy : 0) * W + (in ? gx : 0)];
-    gs[ly][lx] = in ? v : 0.f;
-  }
+// backward: with S = box0(gV)/25 (gV staged and S formed once per tile slot) and E_k = 2 D_k S, v_k = E_k - box0(E_k)/25.
+//   K = 1: out0 (+)= sign * v_0.
+//   K = 2 (D0 = DN, D1 = DH2, out0 = dH3, out1 = dH2x): dH3 += -v_N and dH2x = v_H + v_N -- localvar_bwd(DN, gV, -1,
+//   accumulate), localvar_bwd(DH2, gV, +1) and localvar_bwd(DN, gV, +1, accumulate) with the DN stencil evaluated once and
+//   dH2x written once.
+template <int K>
+__global__ void __launch_bounds__(256) localvar_bwd_kernel(const float* __restrict__ D0, const float* __restrict__ D1,
+                                                           const float* __restrict__ gV, float* __restrict__ out0,
+                                                           float* __restrict__ out1, int C, int H, int W, float sign,
+                                                           int accumulate) {
+  static_assert(K == 1 || K == 2, "one dead buffer per map for the second row sums");
+  __shared__ float gs[1][XH][XW];
+  __shared__ float hs[XH][PW];
+  __shared__ float es[K][PH][PW];
+  const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+  const size_t plane = (size_t)blockIdx.z * H * W;
+  const float* pg = gV + plane;
+  const float* const Dd[2] = {D0, D1};
+  tile_fill<4, 1>(gs, x0, y0, [&](int gy, int gx, float (&g)[1]) {
+    const bool in = in_image(gy, gx, H, W);
+    const float v = pg[(size_t)(in ? gy : 0) * W + (in ? gx : 0)];  // outside: load pixel (0, 0), then select 0
+    g[0] = in ? v : 0.f;
+  });
   __syncthreads();
-  lv_hsum_in(gs, hs, tid);
+  row_sums5<XH, XW, PW, false>(&gs[0][0][0], &hs[0][0]);
   __syncthreads();
-  for (int i = tid; i < LV_DH * LV_DW; i += 256) {
-    const int r = i / LV_DW, cc = i - r * LV_DW;
-    const int gy = y0 + r - 2, gx = x0 + cc - 2;
-    float e_n = 0.f, e_h = 0.f;
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-      const float sum = (((hs[r][cc] + hs[r + 1][cc]) + hs[r + 2][cc]) + hs[r + 3][cc]) + hs[r + 4][cc];
-      const float S = sum / 25.f;
-      e_n = 2.f * pn[(size_t)gy * W + gx] * S;
-      e_h = 2.f * ph[(size_t)gy * W + gx] * S;
-    }
-    en[r][cc] = e_n;
-    eh[r][cc] = e_h;
-  }
-  __syncthreads();
-  float (*hn)[LV_TX] = reinterpret_cast<float (*)[LV_TX]>(&gs[0][0]);      // gs and hs are dead: the second boxes' row sums
-  float (*hh)[LV_TX] = reinterpret_cast<float (*)[LV_TX]>(&hs[0][0]);      // (20 x 64 each) take their place
-  for (int i = tid; i < LV_DH * LV_TX; i += 256) {
-    const int r = i / LV_TX, cc = i - r * LV_TX;
-    hn[r][cc] = (((en[r][cc] + en[r][cc + 1]) + en[r][cc + 2]) + en[r][cc + 3]) + en[r][cc + 4];
-    hh[r][cc] = (((eh[r][cc] + eh[r][cc + 1]) + eh[r][cc + 2]) + eh[r][cc + 3]) + eh[r][cc + 4];
-  }
-  __syncthreads();
-  const int tx = threadIdx.x, gx = x0 + tx;
+  tile_fill<2, K>(es, x0, y0, [&](int gy, int gx, float (&e)[K]) {
+    const bool in = in_image(gy, gx, H, W);
+    const float S = in ? col_sum5<PW>(&hs[gy - y0 + 2][gx - x0 + 2]) / 25.f : 0.f;
 #pragma unroll
-  for (int j = 0; j < LV_TY / 4; ++j) {
-    const int ly = threadIdx.y + 4 * j, gy = y0 + ly;
-    if (gx < W && gy < H) {
-      const float sn = (((hn[ly][tx] + hn[ly + 1][tx]) + hn[ly + 2][tx]) + hn[ly + 3][tx]) + hn[ly + 4][tx];
-      const float sh = (((hh[ly][tx] + hh[ly + 1][tx]) + hh[ly + 2][tx]) + hh[ly + 3][tx]) + hh[ly + 4][tx];
-      const float vn = en[ly + 2][tx + 2] - sn / 25.f, vh = eh[ly + 2][tx + 2] - sh / 25.f;
-      const size_t o = (size_t)c * H * W + (size_t)gy * W + gx;
-      dH3[o] = dH3[o] + -1.f * vn;
-      dH2x[o] = vh + vn;
+    for (int k = 0; k < K; ++k) e[k] = in ? 2.f * Dd[k][plane + (size_t)gy * W + gx] * S : 0.f;
+  });
+  __syncthreads();
+  float* const h2[2] = {&gs[0][0][0], &hs[0][0]};                    // gs and hs are dead: 20 x 64 row sums fit either
+#pragma unroll
+  for (int k = 0; k < K; ++k) row_sums5<PH, PW, TX, false>(&es[k][0][0], h2[k]);
+  __syncthreads();
+  for_owned(x0, y0, H, W, [&](int ly, int lx, int y, int x) {
+    float v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = es[k][ly + 2][lx + 2] - col_sum5<TX>(h2[k] + ly * TX + lx) / 25.f;
+    const size_t o = plane + (size_t)y * W + x;
+    if constexpr (K == 1) {
+      const float r = sign * v[0];
+      out0[o] = accumulate ? out0[o] + r : r;
+    } else {
+      out0[o] = out0[o] + -1.f * v[0];
+      out1[o] = v[1] + v[0];
     }
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ texture mask
@@ -565,7 +453,7 @@ __device__ __forceinline__ float gray144(const float* __restrict__ p, size_t pla
 
 // std over the 5x5 reflect window of a staged gray tile (t[ly + 2][lx + 2] is the pixel): sum first, then the squared
 // deviations in the same index order
-__device__ __forceinline__ float local_std5(const float (*t)[B5_PW], int ly, int lx) {
+__device__ __forceinline__ float local_std5(const float (*t)[PW], int ly, int lx) {
   float v[25];
   float s = 0.f;
   int n = 0;
@@ -591,31 +479,22 @@ __device__ __forceinline__ float local_std5(const float (*t)[B5_PW], int ly, int
 __global__ void __launch_bounds__(256) texture_mask_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            float* __restrict__ mask, float* __restrict__ ratio, int H,
                                                            int W) {
-  __shared__ float ta[B5_PH][B5_PW];
-  __shared__ float tb[B5_PH][B5_PW];
-  const int x0 = blockIdx.x * B5_TX, y0 = blockIdx.y * B5_TY;
-  const int tid = threadIdx.y * 64 + threadIdx.x;
+  __shared__ float t[2][PH][PW];
+  const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
   const size_t plane = (size_t)H * W;
-  for (int i = tid; i < B5_PH * B5_PW; i += 256) {
-    const int sy = i / B5_PW, sx = i - sy * B5_PW;
-    const int gy = y0 + sy - 2, gx = x0 + sx - 2;
-    const size_t o = (size_t)zt_reflect(gy < H + 2 ? gy : H + 1, H) * W + zt_reflect(gx < W + 2 ? gx : W + 1, W);
-    ta[sy][sx] = gray144(a, plane, o);
-    tb[sy][sx] = gray144(b, plane, o);
-  }
+  tile_fill<2, 2>(t, x0, y0, [&](int gy, int gx, float (&v)[2]) {
+    const size_t o = reflect_at(gy, gx, H, W);
+    v[0] = gray144(a, plane, o);
+    v[1] = gray144(b, plane, o);
+  });
   __syncthreads();
-  const int lx = threadIdx.x, x = x0 + lx;
-#pragma unroll
-  for (int j = 0; j < B5_TY / 4; ++j) {
-    const int ly = threadIdx.y + 4 * j, y = y0 + ly;
-    if (x < W && y < H) {
-      float s1 = local_std5(ta, ly, lx), s2 = local_std5(tb, ly, lx);
-      float r = (2.f * s1 * s2) / (s1 * s1 + s2 * s2 + 1e-5f);
-      size_t o = (size_t)y * W + x;
-      mask[o] = r > 0.975f ? 1.f : 0.f;
-      if (ratio) ratio[o] = r;
-    }
-  }
+  for_owned(x0, y0, H, W, [&](int ly, int lx, int y, int x) {
+    float s1 = local_std5(t[0], ly, lx), s2 = local_std5(t[1], ly, lx);
+    float r = (2.f * s1 * s2) / (s1 * s1 + s2 * s2 + 1e-5f);
+    size_t o = (size_t)y * W + x;
+    mask[o] = r > 0.975f ? 1.f : 0.f;
+    if (ratio) ratio[o] = r;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ "YCbCr" over flat memory
@@ -630,7 +509,6 @@ __global__ void __launch_bounds__(256) ycc_flat_kernel(const float* __restrict__
 }
 
 inline dim3 grid2d(int W, int H) { return dim3(zt_cdiv(W, 64), zt_cdiv(H, 4)); }
-inline dim3 grid_b5(int W, int H, int C) { return dim3(zt_cdiv(W, B5_TX), zt_cdiv(H, B5_TY), C); }
 
 }  // namespace
 
@@ -676,7 +554,7 @@ extern "C" int zt_blur21_adj_f32(const float* g, float* tmp, float* dst, const f
 
 extern "C" int zt_box5_reflect_f32(const float* src, float* dst, int C, int H, int W, hipStream_t stream) {
   ZT_REQUIRE(src && dst && H > 2 && W > 2);
-  hipLaunchKernelGGL(box5_reflect_kernel, grid_b5(W, H, C), dim3(64, 4), 0, stream, src, dst, C, H, W);
+  hipLaunchKernelGGL(box5_reflect_kernel, tile_grid(W, H, C), dim3(64, 4), 0, stream, src, dst, C, H, W);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }
@@ -684,7 +562,7 @@ extern "C" int zt_box5_reflect_f32(const float* src, float* dst, int C, int H, i
 extern "C" int zt_box5_reflect_adj_f32(const float* src, float* dst, int C, int H, int W, float scale, int accumulate,
                                        hipStream_t stream) {
   ZT_REQUIRE(src && dst && H > 5 && W > 5);
-  hipLaunchKernelGGL(box5_reflect_adj_kernel, grid_b5(W, H, C), dim3(64, 4), 0, stream, src, dst, C, H, W, scale, accumulate);
+  hipLaunchKernelGGL(box5_reflect_adj_kernel, tile_grid(W, H, C), dim3(64, 4), 0, stream, src, dst, C, H, W, scale, accumulate);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }
@@ -692,8 +570,7 @@ extern "C" int zt_box5_reflect_adj_f32(const float* src, float* dst, int C, int 
 extern "C" int zt_localvar_fwd_f32(const float* a, const float* b, float* D, float* V, int C, int H, int W,
                                    hipStream_t stream) {
   ZT_REQUIRE(a && V && C > 0);
-  dim3 grid(zt_cdiv(W, LV_TX), zt_cdiv(H, LV_TY), C);
-  hipLaunchKernelGGL(localvar_fwd_kernel, grid, dim3(64, 4), 0, stream, a, b, D, V, C, H, W);
+  hipLaunchKernelGGL(localvar_fwd_kernel<1>, tile_grid(W, H, C), dim3(64, 4), 0, stream, a, b, D, V, (float*)nullptr, (float*)nullptr, C, H, W);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }
@@ -701,8 +578,7 @@ extern "C" int zt_localvar_fwd_f32(const float* a, const float* b, float* D, flo
 extern "C" int zt_localvar_bwd_f32(const float* D, const float* gV, float* xbar, int C, int H, int W, float sign,
                                    int accumulate, hipStream_t stream) {
   ZT_REQUIRE(D && gV && xbar && C > 0);
-  dim3 grid(zt_cdiv(W, LV_TX), zt_cdiv(H, LV_TY), C);
-  hipLaunchKernelGGL(localvar_bwd_kernel, grid, dim3(64, 4), 0, stream, D, gV, xbar, C, H, W, sign, accumulate);
+  hipLaunchKernelGGL(localvar_bwd_kernel<1>, tile_grid(W, H, C), dim3(64, 4), 0, stream, D, (const float*)nullptr, gV, xbar, (float*)nullptr, C, H, W, sign, accumulate);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }
@@ -710,7 +586,7 @@ extern "C" int zt_localvar_bwd_f32(const float* D, const float* gV, float* xbar,
 extern "C" int zt_half_bwd_f32(const float* u1, const float* u2, const float* g1, const float* g2, float* dst, int C, int H,
                                int W, hipStream_t stream) {
   ZT_REQUIRE(u1 && u2 && g1 && g2 && dst && C > 0 && H / 2 > 5 && W / 2 > 5);
-  hipLaunchKernelGGL(half_bwd_kernel, grid_b5(W / 2, H / 2, C), dim3(64, 4), 0, stream, u1, u2, g1, g2, dst, C, H, W, H / 2, W / 2);
+  hipLaunchKernelGGL(half_bwd_kernel, tile_grid(W / 2, H / 2, C), dim3(64, 4), 0, stream, u1, u2, g1, g2, dst, C, H, W, H / 2, W / 2);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }
@@ -718,8 +594,7 @@ extern "C" int zt_half_bwd_f32(const float* u1, const float* u2, const float* g1
 extern "C" int zt_localvar_fwd_pair_f32(const float* a, const float* b, float* DA, float* VA, float* DX, float* VX, int C, int H,
                                         int W, hipStream_t stream) {
   ZT_REQUIRE(a && b && DA && VA && DX && VX && C > 0);
-  dim3 grid(zt_cdiv(W, LV_TX), zt_cdiv(H, LV_TY), C);
-  hipLaunchKernelGGL(localvar_fwd_pair_kernel, grid, dim3(64, 4), 0, stream, a, b, DA, VA, DX, VX, C, H, W);
+  hipLaunchKernelGGL(localvar_fwd_kernel<2>, tile_grid(W, H, C), dim3(64, 4), 0, stream, a, b, DA, VA, DX, VX, C, H, W);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }
@@ -727,8 +602,7 @@ extern "C" int zt_localvar_fwd_pair_f32(const float* a, const float* b, float* D
 extern "C" int zt_localvar_bwd_pair_f32(const float* DN, const float* DH2, const float* gV, float* dH3, float* dH2x, int C, int H,
                                         int W, hipStream_t stream) {
   ZT_REQUIRE(DN && DH2 && gV && dH3 && dH2x && C > 0);
-  dim3 grid(zt_cdiv(W, LV_TX), zt_cdiv(H, LV_TY), C);
-  hipLaunchKernelGGL(localvar_bwd_pair_kernel, grid, dim3(64, 4), 0, stream, DN, DH2, gV, dH3, dH2x, C, H, W);
+  hipLaunchKernelGGL(localvar_bwd_kernel<2>, tile_grid(W, H, C), dim3(64, 4), 0, stream, DN, DH2, gV, dH3, dH2x, C, H, W, 0.f, 0);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }
@@ -736,7 +610,7 @@ extern "C" int zt_localvar_bwd_pair_f32(const float* DN, const float* DH2, const
 extern "C" int zt_texture_mask_f32(const float* a, const float* b, float* mask, float* ratio, int H, int W,
                                    hipStream_t stream) {
   ZT_REQUIRE(a && b && mask && H > 2 && W > 2);
-  hipLaunchKernelGGL(texture_mask_kernel, grid_b5(W, H, 1), dim3(64, 4), 0, stream, a, b, mask, ratio, H, W);
+  hipLaunchKernelGGL(texture_mask_kernel, tile_grid(W, H, 1), dim3(64, 4), 0, stream, a, b, mask, ratio, H, W);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }
