@@ -311,6 +311,29 @@ int zt_resample_u8_hwc(const unsigned char* src, unsigned char* dst, int Hi, int
 int zt_u8hwc_to_planar_f32(const unsigned char* src, float* dst, int H, int W, const float* lut256, zt_stream_t stream);
 
 
+/* ---- raw video frames (zt_yuv.hip): 8-bit planar Y'CbCr <-> RGB with chroma resampling, predict.py --y4m_in / --y4m_out -------
+ * A frame is the YUV4MPEG2 payload: plane Y [H][W], then U, then V ([H/2][W/2] for ss 420, [H][W/2] for 422, [H][W] for 444),
+ * contiguous uint8.  ss in {420, 422, 444}; siting 0 = chroma centred between the luma columns it covers (C420jpeg; the only value
+ * for 444), 1 = horizontally co-sited with the left column (C420, C420mpeg2, C420paldv, C422); vertical siting of 420 is always
+ * centred.  W even for 420 / 422, H even for 420; anything else: ZT_EINVAL.  Integer arithmetic, S = 14, bit-exact.
+ * coef: HOST arrays of int32 (read during the call), round(c * 2^14) with matrix and range folded in (zero-tig_amd/y4m.py):
+ *   decode: 6 values yo, CY, CRV, CGU, CGV, CBU; chroma upsampled to 16x integers U16 / V16 (horizontal weights (3, 1) centre or
+ *     4 / (2, 2) left, vertical (3, 1) for 420, clamped at the edges); y = 16 CY (Y - yo), u = U16 - 2048, v = V16 - 2048;
+ *     R = clip8((y + CRV v + 2^17) >> 18), G = clip8((y - CGU u - CGV v + 2^17) >> 18), B = clip8((y + CBU u + 2^17) >> 18).
+ *   encode: 10 values yo, CYR, CYG, CYB, CUR, CUG, CUB, CVR, CVG, CVB; Y = yo + ((CYR R + CYG G + CYB B + 2^13) >> 14);
+ *     U = 128 + ((CUR Rs + CUG Gs + CUB Bs + 2^(13+sh)) >> (14+sh)) over the RGB sums of the footprint (444: the pixel, sh 0; centre:
+ *     the two columns, sh 1; left: [1, 2, 1] over 2c-1, 2c, 2c+1 with -1 clamped to 0, sh 2; 420: both rows, sh + 1); clipped.
+ * zt_yuv_to_rgb_u8: payload -> uint8 [H][W][3] (what zt_resample_u8_hwc takes).
+ * zt_yuv_to_planar_f32: payload -> planar fp32 [3][H][W], value lut256[level] (lut256[k] = float(k) / 255.f); equal to
+ *   zt_yuv_to_rgb_u8 followed by zt_u8hwc_to_planar_f32 bit for bit, without the RGB intermediate and for any H * W.
+ * zt_rgb_f32_to_yuv: planar fp32 [3][H][W] -> payload; levels as zt_quantize_u8_hwc mode 0 makes them, converted in the same pass.
+ * With W % 8 == 0 and 16-byte aligned pointers every access is 4 to 16 bytes wide; otherwise byte accesses, same result. */
+int zt_yuv_to_rgb_u8(const unsigned char* src, unsigned char* dst, int H, int W, int ss, int siting, const int* coef,
+                     zt_stream_t stream);
+int zt_yuv_to_planar_f32(const unsigned char* src, float* dst, int H, int W, int ss, int siting, const int* coef, const float* lut256,
+                         zt_stream_t stream);
+int zt_rgb_f32_to_yuv(const float* src, unsigned char* dst, int H, int W, int ss, int siting, const int* coef, zt_stream_t stream);
+
 /* ---- result PNGs encoded on the device (zt_png.hip) ------------------------------------------------------------------
  * predict.py:57-61, 101-104 (and evals.py's --save_images files): `Image.fromarray(u8).save(path, "PNG")`.  src: uint8 [H][W][3] (what
  * zt_quantize_u8_hwc writes) -> out: a complete zlib stream (78 01, deflate blocks, big-endian Adler-32) of the Paeth-filtered

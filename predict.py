@@ -37,6 +37,16 @@ parser.add_argument("--device_png", type=int, default=0, choices=[0, 1, 2],
                          "2: the same with run-length matches, for frames with flat areas (never larger than 1)")
 parser.add_argument("--timing_json", type=str, default=None,
                     help="write the loop's host-side time split (decode wait, step, copy wait, writer wait) to this file")
+parser.add_argument("--y4m_in", type=str, default=None,
+                    help="raw video in: a YUV4MPEG2 file, or - for standard input (8-bit C420jpeg / C420mpeg2 / C420paldv / C420 / C422 / "
+                         "C444, progressive); replaces the dataset walk, one stream is one sequence; needs --graph 1.  The results "
+                         "are written as <save>/<stem>_enhance.y4m and <stem>_denoise.y4m in the input's own layout")
+parser.add_argument("--y4m_out", type=str, default=None,
+                    help="write the enhance stream here instead (and no denoise stream); - is standard output, every log line then goes to stderr")
+parser.add_argument("--y4m_resize", type=int, default=0, choices=[0, 1],
+                    help="0: enhance at the stream's own size; 1: the loaders' resize((1920, 1080)) first, the output streams are 1920x1080")
+parser.add_argument("--y4m_matrix", type=str, default="bt709", choices=["bt709", "bt601"],
+                    help="the Y'CbCr matrix of the stream (Y4M cannot carry it)")
 
 def save_images(tensor):
     """predict.py:57-61: clip(x * 255, 0, 255).astype(uint8), HWC -- quantised and interleaved on the device (6 MB instead of
@@ -44,8 +54,94 @@ def save_images(tensor):
     return utils.quantize_u8(tensor).cpu().numpy()
 
 
+def main_y4m(args):
+    """--y4m_in: frames come from a Y4M stream and leave as Y4M streams; the colour conversion runs inside the step (InferStep(yuv=))"""
+    import importlib
+    y4m = importlib.import_module("zero-tig_amd.y4m")
+    sink = None
+    if args.y4m_out == "-":                        # standard output carries the stream and nothing else: file descriptor 1 is
+        sink = os.fdopen(os.dup(1), "wb")          # re-pointed at stderr for every print / log line, also of native code
+        sys.stdout.flush()
+        os.dup2(2, 1)
+        sys.stdout = sys.stderr
+    logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(asctime)s %(message)s")
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    dev = torch.device("cuda", args.gpu)
+    reader = y4m.Y4MReader(args.y4m_in)
+    head = reader.header
+    fmt = head.format(args.y4m_matrix)
+    print("Y4M input: %dx%d C%s %s %s" % (head.W, head.H, head.ctag, "full" if head.full else "limited", args.y4m_matrix))
+    model = Finetunemodel(args).to(dev)
+    model.eval()
+    for p in model.parameters():
+        p.requires_grad = False
+    step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080) if args.y4m_resize else None,
+                                                                   yuv=fmt)
+    out_head = head.resized(step.yuv_format.W, step.yuv_format.H)
+    if args.y4m_out is not None:
+        writers = [y4m.Y4MWriter(args.y4m_out, out_head, fh=sink)]
+    else:
+        os.makedirs(args.save, exist_ok=True)
+        stem = "stdin" if args.y4m_in == "-" else os.path.splitext(os.path.basename(args.y4m_in))[0]
+        writers = [y4m.Y4MWriter(os.path.join(args.save, stem + kind), out_head) for kind in ("_enhance.y4m", "_denoise.y4m")]
+    clock = time.perf_counter
+    t = {"decode_wait": 0.0, "step": 0.0, "copy_wait": 0.0, "write": 0.0}
+    frames, t_first = 0, None
+    try:
+        with torch.no_grad():
+            while True:
+                t0 = clock()
+                try:
+                    payload = next(reader)
+                except StopIteration:
+                    break
+                t1 = clock()
+                t_first = t1 if t_first is None else t_first
+                step(payload, frames == 0)
+                reader.release(step.loaded)        # the ring buffer is free once the copy to the device has run
+                t2 = clock()
+                for w, p in zip(writers, step.yuv):    # the copies are ordered on the stream: the next step may overwrite the buffers
+                    w.submit(p)
+                t4 = clock()
+                frames += 1
+                t["decode_wait"] += t1 - t0
+                t["step"] += t2 - t1
+                t["write"] += t4 - t2
+    finally:
+        errors = []
+        for w in writers:                          # every stream is drained; the first failure is the one reported
+            try:
+                w.close()
+            except BaseException as e:             # noqa: BLE001
+                errors.append(e)
+        reader.close()
+        if errors and sys.exc_info()[0] is None:
+            raise errors[0]
+    print("Total frame number: ", frames)
+    if args.timing_json and frames:
+        t_end = clock()                            # the last stream has been closed
+        t["writer_wait"] = sum(w.wait_writer for w in writers)
+        t["write"] -= t["writer_wait"]
+        # the writer threads' own time, summed over the streams: waiting for the step's event (the device) and inside write()
+        t["writer_thread_event"] = sum(w.thread_event for w in writers)
+        t["writer_thread_io"] = sum(w.thread_io for w in writers)
+        per = {k + "_ms": 1e3 * v / frames for k, v in t.items()}
+        with open(args.timing_json, "w") as fh:
+            json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), device_png=0, graph=args.graph,
+                           y4m=1, y4m_resize=args.y4m_resize), fh)
+
+
 def main():
     args = parser.parse_args()
+    if args.y4m_in is None and (args.y4m_out is not None or args.y4m_resize):
+        parser.error("--y4m_out / --y4m_resize need --y4m_in")
+    if args.y4m_in is not None:
+        if not args.graph:
+            parser.error("--y4m_in needs --graph 1 (the colour conversion runs inside InferStep); --graph is %d" % args.graph)
+        if args.device_png:
+            parser.error("--y4m_in writes Y4M streams, not PNG files: --device_png %d cannot be combined with it" % args.device_png)
+        return main_y4m(args)
     os.makedirs(args.save, exist_ok=True)
     logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(asctime)s %(message)s")
     # Finetunemodel builds its RAFT after the weights file is read (model.py:268-290), i.e. with freshly drawn weights: seed them,

@@ -16,10 +16,16 @@
     spread (max - min), and -- the only figure a tree without --timing_json can give -- the differential rate
     (frames - short) / (median wall(frames) - wall(short)) of whole-process runs, which cancels the start-up.
 
+(c) --y4m: raw video instead of PNG files (predict.py --y4m_in / zt_yuv.hip).  The clip's frames, converted by the host encoder of
+    zero-tig_amd/y4m.py (C420mpeg2, limited range, bt709), form one Y4M file; `y4m` in "end_to_end" is predict.py --graph 1
+    --precision bf16 --y4m_in over it (two Y4M streams written), measured like the PNG settings, and "convert" holds the three
+    conversions alone at 1080p: HIP-event median over --reps calls, the bytes each moves and the share of the HBM peak.
+
 This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
 ends the run.  Writes the JSON to --out and prints it as one line.
 Usage: python tools/bench_predict.py [--parent DIR] [--frames 64] [--short 16] [--out profiles/predict_png_1080p.json]
-       python tools/bench_predict.py --skip-encode --frames 256 --short 64 --settings 1 2 --out profiles/predict_png_1080p_256.json"""
+       python tools/bench_predict.py --skip-encode --frames 256 --short 64 --settings 1 2 --out profiles/predict_png_1080p_256.json
+       python tools/bench_predict.py --skip-encode --y4m --frames 256 --short 64 --settings 1 --out profiles/predict_y4m_1080p.json"""
 import argparse
 import importlib
 import json
@@ -85,6 +91,63 @@ def encode_mode(a):
         json.dump(out, fh)
 
 
+# ---- child: the colour conversions alone -------------------------------------------------------------------------------------------
+def convert_mode(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("zero-tig_amd.lib").get_lib()
+    ops = importlib.import_module("zero-tig_amd.ops").Ops(lib)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    y4m = importlib.import_module("zero-tig_amd.y4m")
+    H, W = 1080, 1920
+    fmt = y4m.YuvFormat(W, H, 420, 1, "bt709", 0)
+    rgb = (np.transpose(synth.lowlight_frame(3, H, W)[0], (1, 2, 0)) * 255.0 + 0.5).astype(np.uint8)
+    payload = torch.from_numpy(y4m.encode_host(rgb, fmt)).cuda()
+    x = torch.empty((1, 3, H, W), dtype=torch.float32, device="cuda")
+    u8 = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
+    back = torch.empty_like(payload)
+    calls = {"yuv_to_rgb_u8": (lambda: ops.yuv_to_rgb_u8(payload, fmt, out=u8), fmt.frame_bytes + 3 * H * W),
+             "yuv_to_planar_f32": (lambda: ops.yuv_to_planar_f32(payload, fmt, out=x), fmt.frame_bytes + 12 * H * W),
+             "rgb_f32_to_yuv": (lambda: ops.rgb_f32_to_yuv(x, fmt, out=back), fmt.frame_bytes + 12 * H * W)}
+    out = {"format": "1080x1920 C420mpeg2 limited bt709", "payload_bytes": fmt.frame_bytes}
+    for name, (fn, moved) in calls.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        med = statistics.median(ms)
+        out[name] = {"ms": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "bytes_moved": moved,
+                     "gbs": round(moved / med / 1e6, 1), "hbm_share": round(moved / med / 1e6 / PEAK_HBM_GBS, 4)}
+        print("[bench_predict] convert %s %s" % (name, out[name]), file=sys.stderr, flush=True)
+    with open(a.json, "w") as fh:
+        json.dump(out, fh)
+
+
+def make_y4m(tmp, roots, frames, short, distinct):
+    """the PNG clip's pixels as Y4M files (host encoder; the `distinct` frames encoded once, written round-robin)"""
+    import numpy as np
+    from PIL import Image
+    sys.path.insert(0, ROOT)
+    y4m = importlib.import_module("zero-tig_amd.y4m")
+    head = y4m.Header(1920, 1080, "30:1", "p", None, "420mpeg2", "LIMITED")
+    fmt = head.format("bt709")
+    d = os.path.join(roots["long"], "input", "S01", "low_light_10")
+    pay = [y4m.encode_host(np.asarray(Image.open(os.path.join(d, "%05d.png" % (i + 1)))), fmt) for i in range(min(distinct, frames))]
+    files = {}
+    for name, n in (("long", frames), ("short", short)):
+        files[name] = os.path.join(tmp, "clip_%s.y4m" % name)
+        y4m.write_file(files[name], head, [pay[i % len(pay)] for i in range(n)])
+    return files, fmt.frame_bytes
+
+
 # ---- driver ---------------------------------------------------------------------------------------------------------------------
 def _one_frame(args):
     import numpy as np
@@ -135,7 +198,7 @@ def gpu_step(cmd, limit, env=None, cwd=ROOT):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "encode"])
+    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "encode", "convert"])
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--sizes", type=str, nargs="+", default=["1080x1920", "2160x3840"])
     ap.add_argument("--reps", type=int, default=30)
@@ -145,6 +208,9 @@ def main():
     ap.add_argument("--settings", type=int, nargs="+", default=[0, 1, 2], choices=[0, 1, 2],
                     help="the --device_png values of part (b); a longer clip (--frames 256 --short 64 --settings 1 2) narrows the spread")
     ap.add_argument("--skip-encode", action="store_true", help="part (b) only")
+    ap.add_argument("--short-repeats", type=int, default=1,
+                    help="runs over the --short inputs per setting; the differential rate uses their median (one run leaves it noisy)")
+    ap.add_argument("--y4m", action="store_true", help="part (c): the Y4M loop next to the PNG settings, and the conversions alone")
     ap.add_argument("--repeats", type=int, default=3, help="runs over the --frames inputs per setting (the spread between them is reported)")
     ap.add_argument("--distinct", type=int, default=8)
     ap.add_argument("--step-timeout", type=int, default=300)
@@ -152,11 +218,22 @@ def main():
     a = ap.parse_args()
     if a.mode == "encode":
         return encode_mode(a)
+    if a.mode == "convert":
+        return convert_mode(a)
     out = {"what": "predict.py --graph 1 --precision bf16 over %d synthetic 1080p PNG inputs (%d distinct): frames per second from the "
                    "first frame read to the last file closed (timing_json), the differential whole-process rate over %d and %d "
                    "frames, and the host-side split per frame, %d runs per setting; encode = Ops.png_encode alone, mode 1 and 2, "
                    "HIP-event median of %d calls" % (a.frames, a.distinct, a.frames, a.short, a.repeats, a.reps),
            "cpus": len(os.sched_getaffinity(0)), "peak_hbm_gbs": PEAK_HBM_GBS}
+    out["what"] += ("; loop.decode_wait_ms includes the wait for the FIRST frame (loader start-up), which `seconds` / `fps` exclude: "
+                    "loop.decode_wait_steady_ms_max = (seconds - frames * (step + copy_wait + write + writer_wait)) / (frames - 1) "
+                    "bounds the wait per frame after the first; differential_fps from the medians of %d short and %d long runs"
+                    % (a.short_repeats, a.repeats))
+    if a.y4m:
+        out["what"] += ("; y4m = the same loop over the clip's pixels as one Y4M file (C420mpeg2, limited, bt709; host encoder), "
+                        "predict.py --y4m_in, two Y4M streams written; its loop.writer_thread_event_ms / writer_thread_io_ms = the "
+                        "two writer threads' time per frame waiting for the step's event / inside write(); convert = "
+                        "Ops.yuv_to_rgb_u8, yuv_to_planar_f32, rgb_f32_to_yuv alone at 1080p, HIP-event median of %d calls" % a.reps)
     tmp = tempfile.mkdtemp(prefix="zt_bench_predict_")
     try:
         if not a.skip_encode:
@@ -164,25 +241,34 @@ def main():
             gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "encode", "--json", ej, "--reps", str(a.reps), "--sizes"]
                      + a.sizes, a.step_timeout)
             out["encode"] = json.load(open(ej))
+        if a.y4m:
+            cj = os.path.join(tmp, "convert.json")
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "convert", "--json", cj, "--reps", str(a.reps)], a.step_timeout)
+            out["convert"] = json.load(open(cj))
         roots, weights = make_clip(tmp, a.frames, a.short, a.distinct)
+        y4m_files = make_y4m(tmp, roots, a.frames, a.short, a.distinct)[0] if a.y4m else None
         so = os.path.join(ROOT, "zero-tig_amd", "libzerotig_hip.so")
         configs = ([("parent", a.parent, [])] if a.parent else []) + [("device_png_%d" % v, ROOT, ["--device_png", str(v)])
                                                                       for v in a.settings]
+        if a.y4m:
+            configs.append(("y4m", ROOT, ["--y4m_in"]))
         out["end_to_end"] = {}
         for name, tree, extra in configs:
             env = dict(os.environ, PYTHONPATH=tree, ZEROTIG_HIP_LIB=so)
             row, wall, loops = {}, {"short": [], "long": []}, []
-            for which, n, times in (("short", a.short, 1), ("long", a.frames, a.repeats)):
+            for which, n, times in (("short", a.short, a.short_repeats), ("long", a.frames, a.repeats)):
                 for _ in range(times):
                     save = os.path.join(tmp, "out_%s_%s" % (name, which))
                     cmd = [sys.executable, "predict.py", "--dataset", "RLV", "--lowlight_images_path", roots[which], "--model_pretrain",
                            weights, "--save", save, "--graph", "1", "--precision", "bf16"] + extra
+                    if name == "y4m":
+                        cmd.append(y4m_files[which])
                     tj = os.path.join(tmp, "timing_%s_%s.json" % (name, which))
                     if extra:
                         cmd += ["--timing_json", tj]
                     wall[which].append(gpu_step(cmd, a.step_timeout, env=env, cwd=tree))
                     written = sum(len(fs) for _, _, fs in os.walk(save))
-                    assert written == 2 * n, (name, which, written)
+                    assert written == (2 if name == "y4m" else 2 * n), (name, which, written)
                     if which == "long":
                         row["output_bytes_per_frame"] = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(save) for f in fs) // n
                         if extra:
@@ -192,11 +278,15 @@ def main():
             if loops:
                 fps = [l["fps"] for l in loops]
                 row["loop"] = sorted(loops, key=lambda l: l["fps"])[len(loops) // 2]          # the median run's split
+                lp = row["loop"]
+                busy = sum(lp.get(k, 0.0) for k in ("step_ms", "copy_wait_ms", "write_ms", "writer_wait_ms"))
+                if lp["frames"] > 1:
+                    lp["decode_wait_steady_ms_max"] = max(0.0, (1e3 * lp["seconds"] - lp["frames"] * busy) / (lp["frames"] - 1))
                 row["fps_runs"] = [round(v, 2) for v in fps]
                 row["fps_median"] = round(statistics.median(fps), 2)
                 row["fps_spread"] = round(max(fps) - min(fps), 2)
             row["wall_s"] = {k: [round(v, 2) for v in vs] for k, vs in wall.items()}
-            row["differential_fps"] = round((a.frames - a.short) / (statistics.median(wall["long"]) - wall["short"][0]), 2)
+            row["differential_fps"] = round((a.frames - a.short) / (statistics.median(wall["long"]) - statistics.median(wall["short"])), 2)
             out["end_to_end"][name] = row
             print("[bench_predict] %s %s" % (name, row), file=sys.stderr, flush=True)
     finally:

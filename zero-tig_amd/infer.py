@@ -30,13 +30,26 @@ class InferStep:
     THE RETURNED TENSORS, `step.u8` AND `step.png` LIVE IN THE STEP'S (GRAPH'S) BUFFERS: they are valid until the next call; copy what must
     survive it.  The model must not be moved, and `last_H3 / last_s3` not re-assigned by the caller, after the capture.
 
+    yuv=fmt (a `y4m.YuvFormat`: W, H, subsampling, chroma siting, matrix, range): `frame` is the 1-D uint8 payload of a raw video
+    frame (planes Y, U, V), pinned or on the device.  It is copied into a static device buffer (`step.loaded` is the event behind
+    that copy: the host buffer may be reused once it has completed) and converted inside the step -- `Ops.yuv_to_planar_f32`
+    straight into the input when `ingest_size` is None or (W, H), `Ops.yuv_to_rgb_u8` + `Ops.ingest_u8` otherwise -- and
+    `step.yuv = (enhance_payload, denoise_payload)` holds the two results as payloads of the SAME subsampling, siting, matrix and
+    range at the output size (`step.yuv_format`), made from H2 / H3 by `Ops.rgb_f32_to_yuv`.  All of it is part of the captured
+    graph; `step.u8` / `step.png` are filled as without it.
+
     Weights are prepared again when a parameter or BatchNorm buffer changed (`_version` / `data_ptr()` of the tensors, e.g. after
     `load_state_dict`); the prepared buffers keep their addresses, so a captured graph stays valid across a reload."""
 
-    def __init__(self, model, use_graph=True, ingest_size=(1920, 1080), png=False):
+    def __init__(self, model, use_graph=True, ingest_size=(1920, 1080), png=False, yuv=None):
         assert int(png) in (0, 1, 2), png
         self.model, self.use_graph, self.ingest_size, self.want_png = model, use_graph, ingest_size, int(png)
         self.graph, self.x, self.out, self.u8, self.png = None, None, None, None, None
+        self.fmt, self.yuv, self.yuv_format, self.loaded, self._payload = yuv, None, None, None, None
+        if yuv is not None:
+            yuv.check()
+            W, H = (yuv.W, yuv.H) if ingest_size is None else ingest_size
+            self.yuv_format = yuv.resized(W, H).check()          # the output streams: same layout at the output size
         self.n_eager_steady, self.n_captures, self.n_prepares = 0, 0, 0
         self._wp, self._wsig, self._bound = None, None, None
 
@@ -72,8 +85,27 @@ class InferStep:
         out.copy_(frame, non_blocking=True)
         return out
 
-    def _body(self, eng, rp, x):
+    def _load_yuv(self, frame, dev):
+        """payload -> the device buffer the conversion reads (static when the step is graph-replayed)"""
+        assert frame.dtype == torch.uint8 and frame.dim() == 1 and frame.numel() == self.fmt.frame_bytes, \
+            (frame.dtype, tuple(frame.shape), self.fmt.frame_bytes)
+        if self._payload is None or self._payload.device != dev:
+            self._payload = torch.empty(self.fmt.frame_bytes, dtype=torch.uint8, device=dev)
+        self._payload.copy_(frame, non_blocking=True)
+        self.loaded = torch.cuda.Event()
+        self.loaded.record()
+        return self._payload
+
+    def _decode(self, ops, payload, x):
+        """the payload in `self._payload` -> the model's input (x: the static input buffer, or None)"""
+        if self.yuv_format[:2] == self.fmt[:2]:
+            return ops.yuv_to_planar_f32(payload, self.fmt, out=x)
+        return ops.ingest_u8(ops.yuv_to_rgb_u8(payload, self.fmt), out=x, size=self.ingest_size)
+
+    def _body(self, eng, rp, x, payload=None):
         m = self.model
+        if payload is not None:
+            x = self._decode(eng.ops, payload, x)
         new = m.is_new_seq or m.last_H3 is None
         cache_fn = None if new else (lambda L2: rp.update_cache(m.last_H3, m.last_s3, L2, m.of_scale))
         H2, H3, s3 = eng.forward_stream(x, cache_fn, self._wp)
@@ -81,7 +113,8 @@ class InferStep:
         m.update_H3(H3, s3)
         u8 = (eng.ops.quantize_u8(H2, 0), eng.ops.quantize_u8(H3, 0))
         png = tuple(eng.ops.png_encode(u, mode=self.want_png) for u in u8) if self.want_png else None
-        return (H2, H3, s3), u8, png
+        yuv = None if payload is None else (eng.ops.rgb_f32_to_yuv(H2, self.yuv_format), eng.ops.rgb_f32_to_yuv(H3, self.yuv_format))
+        return (H2, H3, s3), u8, png, yuv
 
     def __call__(self, frame, is_new_seq=False):
         m = self.model
@@ -89,10 +122,13 @@ class InferStep:
         dev = m._trainable()[0][1].device
         eng, rp = self._prepare()
         with torch.no_grad():
+            payload = None if self.fmt is None else self._load_yuv(frame, dev)
             if not self.use_graph:
-                self.out, self.u8, self.png = self._body(eng, rp, self._load(frame, dev))
+                self.out, self.u8, self.png, self.yuv = self._body(eng, rp, None if self.fmt else self._load(frame, dev), payload)
                 return self.out
-            if frame.dtype == torch.uint8:
+            if self.fmt is not None:
+                shape = (1, 3, self.yuv_format.H, self.yuv_format.W)
+            elif frame.dtype == torch.uint8:
                 Wi, Hi = self.ingest_size if self.ingest_size is not None else (frame.shape[-2], frame.shape[-3])
                 shape = (1, 3, Hi, Wi)
             else:
@@ -102,21 +138,22 @@ class InferStep:
             if self.x is None:
                 self.x = torch.empty(shape, dtype=torch.float32, device=dev)
                 m.enable_static_cache(shape)
-            self._load(frame, dev, out=self.x)
+            if self.fmt is None:
+                self._load(frame, dev, out=self.x)
             if is_new_seq or m.last_H3 is None or self.n_eager_steady < 1:
                 # eager: new-sequence frames, and the first steady-state frame (loads every kernel's code object and sizes the
                 # RAFT plan's buffers before anything is captured)
                 if not (is_new_seq or m.last_H3 is None):
                     self.n_eager_steady += 1
-                self.out, self.u8, self.png = self._body(eng, rp, self.x)
+                self.out, self.u8, self.png, self.yuv = self._body(eng, rp, self.x, payload)
                 return self.out
             if self.graph is None:
                 torch.cuda.synchronize(dev)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._gout = self._body(eng, rp, self.x)
+                    self._gout = self._body(eng, rp, self.x, payload)
                 self.graph = g
                 self.n_captures += 1
             self.graph.replay()
-            self.out, self.u8, self.png = self._gout
+            self.out, self.u8, self.png, self.yuv = self._gout
             return self.out

@@ -235,6 +235,14 @@ class Ops:
         self.lib.call("zt_png_code_lengths", h, out, self._s(h))
         return out
 
+    def _to_tensor_lut(self, dev):
+        """the 256-entry ToTensor table (`ingest.to_tensor_lut`) on `dev`, uploaded once"""
+        from . import ingest
+        cache = self.__dict__.setdefault("_ingest_tables", {})
+        if ("lut", str(dev)) not in cache:
+            cache[("lut", str(dev))] = torch.from_numpy(ingest.to_tensor_lut()).to(dev)
+        return cache[("lut", str(dev))]
+
     def ingest_u8(self, u8, out=None, size=(1920, 1080)):
         """Decoded frame, uint8 [H0,W0,3] (or [1,H0,W0,3]) on the device -> fp32 [1,3,H,W] in [0,1]: the reference loader's
         `im.resize(size)` (PIL BICUBIC, 8-bit two-pass; skipped when the frame already has that size, as PIL does) followed by
@@ -255,8 +263,6 @@ class Ops:
                 coef, bounds, ks = ingest.pil_bicubic_tables(n_in, n_out)
                 cache[key] = (torch.from_numpy(coef).to(dev), torch.from_numpy(bounds).to(dev), ks)
             return cache[key]
-        if ("lut", str(dev)) not in cache:
-            cache[("lut", str(dev))] = torch.from_numpy(ingest.to_tensor_lut()).to(dev)
         cur = u8
         if W0 != W:                                           # Resample.c: horizontal pass first, into an 8-bit image
             coef, bounds, ks = tables(W0, W)
@@ -271,7 +277,47 @@ class Ops:
         if out is None:
             out = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
         assert tuple(out.shape) == (1, 3, H, W) and out.dtype == torch.float32 and out.is_contiguous()
-        self.lib.call("zt_u8hwc_to_planar_f32", cur, out, H, W, cache[("lut", str(dev))], s)
+        self.lib.call("zt_u8hwc_to_planar_f32", cur, out, H, W, self._to_tensor_lut(dev), s)
+        return out
+
+    # ---- raw video frames (zt_yuv.hip) --------------------------------------------------------------------------
+    def _yuv_payload(self, payload, fmt):
+        fmt.check()
+        assert payload.dtype == torch.uint8 and payload.dim() == 1 and payload.is_contiguous() and payload.numel() == fmt.frame_bytes, \
+            (payload.dtype, tuple(payload.shape), fmt.frame_bytes)
+
+    def yuv_to_rgb_u8(self, payload, fmt, out=None):
+        """Y4M payload (1-D uint8: planes Y, U, V of `fmt`, a `y4m.YuvFormat`) -> uint8 [H,W,3] RGB on the device: chroma
+        upsampled for the format's siting and the integer matrix of DESIGN 8d, bit-exact."""
+        self._yuv_payload(payload, fmt)
+        if out is None:
+            out = torch.empty((fmt.H, fmt.W, 3), dtype=torch.uint8, device=payload.device)
+        assert tuple(out.shape) == (fmt.H, fmt.W, 3) and out.dtype == torch.uint8 and out.is_contiguous()
+        self.lib.call("zt_yuv_to_rgb_u8", payload, out, fmt.H, fmt.W, fmt.ss, fmt.siting, fmt.decode_coef(), self._s(payload))
+        return out
+
+    def yuv_to_planar_f32(self, payload, fmt, out=None):
+        """Y4M payload -> fp32 [1,3,H,W] in [0,1]: `ingest_u8(yuv_to_rgb_u8(payload), size=None)` bit for bit in one pass (no RGB
+        intermediate, any H * W)."""
+        self._yuv_payload(payload, fmt)
+        dev = payload.device
+        if out is None:
+            out = torch.empty((1, 3, fmt.H, fmt.W), dtype=torch.float32, device=dev)
+        assert tuple(out.shape) == (1, 3, fmt.H, fmt.W) and out.dtype == torch.float32 and out.is_contiguous()
+        self.lib.call("zt_yuv_to_planar_f32", payload, out, fmt.H, fmt.W, fmt.ss, fmt.siting, fmt.decode_coef(),
+                      self._to_tensor_lut(dev), self._s(payload))
+        return out
+
+    def rgb_f32_to_yuv(self, x, fmt, out=None):
+        """[1,3,H,W] fp32 in [0,1] -> Y4M payload (1-D uint8) of `fmt`: the levels `quantize_u8(x, 0)` makes (predict.py's
+        truncation), converted and chroma-subsampled in the same pass."""
+        _f32c(x)
+        fmt.check()
+        assert tuple(x.shape) == (1, 3, fmt.H, fmt.W), (tuple(x.shape), fmt)
+        if out is None:
+            out = torch.empty(fmt.frame_bytes, dtype=torch.uint8, device=x.device)
+        assert out.dtype == torch.uint8 and out.dim() == 1 and out.numel() == fmt.frame_bytes and out.is_contiguous()
+        self.lib.call("zt_rgb_f32_to_yuv", x, out, fmt.H, fmt.W, fmt.ss, fmt.siting, fmt.encode_coef(), self._s(x))
         return out
 
     def psnr_u8(self, a, b):
