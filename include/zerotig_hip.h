@@ -334,6 +334,17 @@ int zt_yuv_to_planar_f32(const unsigned char* src, float* dst, int H, int W, int
                          zt_stream_t stream);
 int zt_rgb_f32_to_yuv(const float* src, unsigned char* dst, int H, int W, int ss, int siting, const int* coef, zt_stream_t stream);
 
+/* ---- scene cuts in a raw video stream (zt_scene.hip): predict.py --y4m_scene_cut, zero-tig_amd/scenecut.py, DESIGN 8e ------------
+ * zt_luma_grid_u8: the luma plane y [H][W] (the first H * W bytes of a payload) in 16 x 16 cells, gh = ceil(H / 16) rows of
+ *   gw = ceil(W / 16), edge cells holding the pixels that exist: grid[i * gw + j] = sum over the cell of max(y - yo, 0), at most
+ *   256 * 255.  yo in 0..255 (16 for limited range, 0 for full range).  16-byte loads when W % 16 == 0 and y is 16-byte aligned,
+ *   byte loads otherwise, same result.
+ * zt_grid_sad_u32: out2[0] = sum |a[k] - b[k]|, out2[1] = sum (a[k] + b[k]) over k < n, 64-bit sums; out2 is overwritten, the
+ *   caller zeroes nothing.
+ * Integer and deterministic (no atomics).  H, W or n <= 0, yo outside 0..255: ZT_EINVAL. */
+int zt_luma_grid_u8(const unsigned char* y, int H, int W, int yo, unsigned int* grid /* [gh*gw] */, zt_stream_t stream);
+int zt_grid_sad_u32(const unsigned int* a, const unsigned int* b, int n, unsigned long long* out2 /* sad, tot */, zt_stream_t stream);
+
 /* ---- result PNGs encoded on the device (zt_png.hip) ------------------------------------------------------------------
  * predict.py:57-61, 101-104 (and evals.py's --save_images files): `Image.fromarray(u8).save(path, "PNG")`.  src: uint8 [H][W][3] (what
  * zt_quantize_u8_hwc writes) -> out: a complete zlib stream (78 01, deflate blocks, big-endian Adler-32) of the Paeth-filtered

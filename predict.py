@@ -47,6 +47,13 @@ parser.add_argument("--y4m_resize", type=int, default=0, choices=[0, 1],
                     help="0: enhance at the stream's own size; 1: the loaders' resize((1920, 1080)) first, the output streams are 1920x1080")
 parser.add_argument("--y4m_matrix", type=str, default="bt709", choices=["bt709", "bt601"],
                     help="the Y'CbCr matrix of the stream (Y4M cannot carry it)")
+parser.add_argument("--y4m_scene_cut", type=float, default=0.0,
+                    help="0: one stream is one sequence; T > 0: a frame whose scene score (DESIGN 8e: relative change of the luma's "
+                         "16 x 16 cell sums against the previous frame, computed on the device on a stream of its own) exceeds T "
+                         "starts a new sequence, i.e. the recurrent cache restarts there.  Suggested: 0.03, set from synthetic "
+                         "clips only (cuts between unrelated low-light scenes), not validated on real footage")
+parser.add_argument("--y4m_cuts_json", type=str, default=None,
+                    help="write {threshold, cuts: [frame indices], score: [...], rel: [...]} here at the end; needs --y4m_scene_cut and --y4m_in")
 
 def save_images(tensor):
     """predict.py:57-61: clip(x * 255, 0, 255).astype(uint8), HWC -- quantised and interleaved on the device (6 MB instead of
@@ -79,6 +86,10 @@ def main_y4m(args):
     step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080) if args.y4m_resize else None,
                                                                    yuv=fmt)
     out_head = head.resized(step.yuv_format.W, step.yuv_format.H)
+    det, cuts, scores, rels = None, [], [], []
+    if args.y4m_scene_cut > 0:
+        det = importlib.import_module("zero-tig_amd.scenecut").SceneCut(
+            importlib.import_module("zero-tig_amd.ops").Ops(importlib.import_module("zero-tig_amd.lib").get_lib()), dev, fmt, args.y4m_scene_cut)
     if args.y4m_out is not None:
         writers = [y4m.Y4MWriter(args.y4m_out, out_head, fh=sink)]
     else:
@@ -98,7 +109,16 @@ def main_y4m(args):
                     break
                 t1 = clock()
                 t_first = t1 if t_first is None else t_first
-                step(payload, frames == 0)
+                if det is None:
+                    step(payload, frames == 0)
+                else:                              # the detector's own stream; its copy has completed when pop() returns
+                    det.push(payload)
+                    is_cut, score, rel = det.pop()
+                    scores.append(score), rels.append(rel)
+                    if is_cut and frames:
+                        cuts.append(frames)
+                        logging.info("scene cut at frame %d: score %.4f (rel %.4f) > %g", frames, score, rel, args.y4m_scene_cut)
+                    step(payload, frames == 0 or is_cut)
                 reader.release(step.loaded)        # the ring buffer is free once the copy to the device has run
                 t2 = clock()
                 for w, p in zip(writers, step.yuv):    # the copies are ordered on the stream: the next step may overwrite the buffers
@@ -119,6 +139,9 @@ def main_y4m(args):
         if errors and sys.exc_info()[0] is None:
             raise errors[0]
     print("Total frame number: ", frames)
+    if args.y4m_cuts_json:
+        with open(args.y4m_cuts_json, "w") as fh:
+            json.dump({"threshold": args.y4m_scene_cut, "cuts": cuts, "score": scores, "rel": rels}, fh)
     if args.timing_json and frames:
         t_end = clock()                            # the last stream has been closed
         t["writer_wait"] = sum(w.wait_writer for w in writers)
@@ -126,16 +149,26 @@ def main_y4m(args):
         # the writer threads' own time, summed over the streams: waiting for the step's event (the device) and inside write()
         t["writer_thread_event"] = sum(w.thread_event for w in writers)
         t["writer_thread_io"] = sum(w.thread_io for w in writers)
+        extra = {}
+        if det is not None:                        # part of `step`: the seconds pop() was blocked
+            t["scene_wait"] = det.wait
+            extra["cuts"] = len(cuts)
         per = {k + "_ms": 1e3 * v / frames for k, v in t.items()}
         with open(args.timing_json, "w") as fh:
             json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), device_png=0, graph=args.graph,
-                           y4m=1, y4m_resize=args.y4m_resize), fh)
+                           y4m=1, y4m_resize=args.y4m_resize, **extra), fh)
 
 
 def main():
     args = parser.parse_args()
     if args.y4m_in is None and (args.y4m_out is not None or args.y4m_resize):
         parser.error("--y4m_out / --y4m_resize need --y4m_in")
+    if args.y4m_scene_cut < 0:
+        parser.error("--y4m_scene_cut is a threshold in [0, 1], 0 = off; got %g" % args.y4m_scene_cut)
+    if args.y4m_scene_cut > 0 and args.y4m_in is None:
+        parser.error("--y4m_scene_cut needs --y4m_in")
+    if args.y4m_cuts_json is not None and not (args.y4m_scene_cut > 0 and args.y4m_in is not None):
+        parser.error("--y4m_cuts_json needs --y4m_scene_cut T (T > 0) and --y4m_in")
     if args.y4m_in is not None:
         if not args.graph:
             parser.error("--y4m_in needs --graph 1 (the colour conversion runs inside InferStep); --graph is %d" % args.graph)

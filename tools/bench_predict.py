@@ -20,12 +20,17 @@
     zero-tig_amd/y4m.py (C420mpeg2, limited range, bt709), form one Y4M file; `y4m` in "end_to_end" is predict.py --graph 1
     --precision bf16 --y4m_in over it (two Y4M streams written), measured like the PNG settings, and "convert" holds the three
     conversions alone at 1080p: HIP-event median over --reps calls, the bytes each moves and the share of the HBM peak.
+    --scene-cut T [T ..]: the same loop with predict.py --y4m_scene_cut T as "y4m_scene_cut_T", its runs alternating with those of
+    "y4m" (flag off), with the time the loop was blocked for the detector (scene_wait_ms) and the sequences restarted (cuts); "scene"
+    holds the two kernels of zt_scene.hip alone.
 
 This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
 ends the run.  Writes the JSON to --out and prints it as one line.
 Usage: python tools/bench_predict.py [--parent DIR] [--frames 64] [--short 16] [--out profiles/predict_png_1080p.json]
        python tools/bench_predict.py --skip-encode --frames 256 --short 64 --settings 1 2 --out profiles/predict_png_1080p_256.json
-       python tools/bench_predict.py --skip-encode --y4m --frames 256 --short 64 --settings 1 --out profiles/predict_y4m_1080p.json"""
+       python tools/bench_predict.py --skip-encode --y4m --frames 256 --short 64 --settings 1 --out profiles/predict_y4m_1080p.json
+       python tools/bench_predict.py --skip-encode --y4m --scene-cut 0.5 0.03 --frames 256 --short 64 --settings \
+                                     --out profiles/predict_y4m_scene_cut_1080p.json"""
 import argparse
 import importlib
 import json
@@ -131,6 +136,54 @@ def convert_mode(a):
         json.dump(out, fh)
 
 
+# ---- child: the scene-cut kernels alone -----------------------------------------------------------------------------------------------
+def scene_mode(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("zero-tig_amd.lib").get_lib()
+    ops = importlib.import_module("zero-tig_amd.ops").Ops(lib)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    y4m = importlib.import_module("zero-tig_amd.y4m")
+    H, W = 1080, 1920
+    fmt = y4m.YuvFormat(W, H, 420, 1, "bt709", 0)
+    pay = []
+    for t in (3, 4):
+        rgb = (np.transpose(synth.lowlight_frame(t, H, W)[0], (1, 2, 0)) * 255.0 + 0.5).astype(np.uint8)
+        pay.append(torch.from_numpy(y4m.encode_host(rgb, fmt)).cuda())
+    shifted = torch.empty(H * W + 1, dtype=torch.uint8, device="cuda")[1:]      # one byte off a 16-byte boundary: the byte path
+    shifted.copy_(pay[0][:H * W])
+    cells = ((H + 15) // 16) * ((W + 15) // 16)
+    g = [torch.empty(cells, dtype=torch.int32, device="cuda") for _ in range(3)]
+    pair = torch.empty(2, dtype=torch.int64, device="cuda")
+    ops.luma_grid(pay[1], fmt, out=g[1])
+    calls = {"luma_grid_16_byte_loads": (lambda: ops.luma_grid(pay[0], fmt, out=g[0]), H * W + 4 * cells),
+             "luma_grid_byte_loads": (lambda: ops.luma_grid(shifted, fmt, out=g[2]), H * W + 4 * cells),
+             "grid_sad": (lambda: ops.grid_sad(g[0], g[1], out=pair), 8 * cells + 16)}
+    out = {"format": "1080x1920 luma plane, 68 x 120 cells", "cells": cells}
+    for name, (fn, moved) in calls.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        med = statistics.median(ms)
+        out[name] = {"ms": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "bytes_moved": moved,
+                     "gbs": round(moved / med / 1e6, 1)}
+        print("[bench_predict] scene %s %s" % (name, out[name]), file=sys.stderr, flush=True)
+    assert torch.equal(g[0], g[2]), "the byte path and the 16-byte path disagree"
+    sad, tot = pair.tolist()
+    out["pair_of_frames_3_4"] = {"sad": sad, "tot": tot, "rel": sad / max(tot, 1)}
+    with open(a.json, "w") as fh:
+        json.dump(out, fh)
+
+
 def make_y4m(tmp, roots, frames, short, distinct):
     """the PNG clip's pixels as Y4M files (host encoder; the `distinct` frames encoded once, written round-robin)"""
     import numpy as np
@@ -198,19 +251,25 @@ def gpu_step(cmd, limit, env=None, cwd=ROOT):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "encode", "convert"])
+    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "encode", "convert", "scene"])
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--sizes", type=str, nargs="+", default=["1080x1920", "2160x3840"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--parent", type=str, default=None, help="checkout of the parent commit (runs against this tree's library)")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--short", type=int, default=16)
-    ap.add_argument("--settings", type=int, nargs="+", default=[0, 1, 2], choices=[0, 1, 2],
-                    help="the --device_png values of part (b); a longer clip (--frames 256 --short 64 --settings 1 2) narrows the spread")
+    ap.add_argument("--settings", type=int, nargs="*", default=[0, 1, 2], choices=[0, 1, 2],
+                    help="the --device_png values of part (b); a longer clip (--frames 256 --short 64 --settings 1 2) narrows the spread; "
+                         "none: the PNG loop is not run")
     ap.add_argument("--skip-encode", action="store_true", help="part (b) only")
     ap.add_argument("--short-repeats", type=int, default=1,
                     help="runs over the --short inputs per setting; the differential rate uses their median (one run leaves it noisy)")
     ap.add_argument("--y4m", action="store_true", help="part (c): the Y4M loop next to the PNG settings, and the conversions alone")
+    ap.add_argument("--scene-cut", type=float, nargs="+", default=[],
+                    help="with --y4m: also the Y4M loop with predict.py --y4m_scene_cut T for each T given (settings y4m_scene_cut_T, next "
+                         "to y4m = flag off, the runs alternating), their loop.scene_wait_ms and loop.cuts, and scene = the two kernels "
+                         "of zt_scene.hip alone at 1080p.  The clip repeats --distinct frames, and the jump back to the first one scores "
+                         "0.054: a T above that measures the detector alone, a T below it also a restarted sequence every --distinct frames")
     ap.add_argument("--repeats", type=int, default=3, help="runs over the --frames inputs per setting (the spread between them is reported)")
     ap.add_argument("--distinct", type=int, default=8)
     ap.add_argument("--step-timeout", type=int, default=300)
@@ -220,6 +279,8 @@ def main():
         return encode_mode(a)
     if a.mode == "convert":
         return convert_mode(a)
+    if a.mode == "scene":
+        return scene_mode(a)
     out = {"what": "predict.py --graph 1 --precision bf16 over %d synthetic 1080p PNG inputs (%d distinct): frames per second from the "
                    "first frame read to the last file closed (timing_json), the differential whole-process rate over %d and %d "
                    "frames, and the host-side split per frame, %d runs per setting; encode = Ops.png_encode alone, mode 1 and 2, "
@@ -245,6 +306,13 @@ def main():
             cj = os.path.join(tmp, "convert.json")
             gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "convert", "--json", cj, "--reps", str(a.reps)], a.step_timeout)
             out["convert"] = json.load(open(cj))
+        if a.y4m and a.scene_cut:
+            sj = os.path.join(tmp, "scene.json")
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "scene", "--json", sj, "--reps", str(a.reps)], a.step_timeout)
+            out["scene"] = json.load(open(sj))
+            out["what"] += ("; y4m_scene_cut_T = the y4m loop with --y4m_scene_cut T (loop.scene_wait_ms = the time pop() was blocked, part "
+                            "of step_ms; loop.cuts = sequences restarted), its runs alternating with those of y4m; scene = "
+                            "Ops.luma_grid (16-byte and byte loads) and Ops.grid_sad alone, HIP-event median of %d calls" % a.reps)
         roots, weights = make_clip(tmp, a.frames, a.short, a.distinct)
         y4m_files = make_y4m(tmp, roots, a.frames, a.short, a.distinct)[0] if a.y4m else None
         so = os.path.join(ROOT, "zero-tig_amd", "libzerotig_hip.so")
@@ -252,29 +320,42 @@ def main():
                                                                       for v in a.settings]
         if a.y4m:
             configs.append(("y4m", ROOT, ["--y4m_in"]))
+            for T in a.scene_cut:
+                configs.append(("y4m_scene_cut_%g" % T, ROOT, ["--y4m_scene_cut", str(T), "--y4m_in"]))
         out["end_to_end"] = {}
-        for name, tree, extra in configs:
+        state = {name: ({}, {"short": [], "long": []}, []) for name, _, _ in configs}
+
+        def run_once(name, tree, extra, which, n):
+            row, wall, loops = state[name]
+            is_y4m = name.startswith("y4m")
             env = dict(os.environ, PYTHONPATH=tree, ZEROTIG_HIP_LIB=so)
-            row, wall, loops = {}, {"short": [], "long": []}, []
+            save = os.path.join(tmp, "out_%s_%s" % (name, which))
+            cmd = [sys.executable, "predict.py", "--dataset", "RLV", "--lowlight_images_path", roots[which], "--model_pretrain",
+                   weights, "--save", save, "--graph", "1", "--precision", "bf16"] + extra
+            if is_y4m:
+                cmd.append(y4m_files[which])
+            tj = os.path.join(tmp, "timing_%s_%s.json" % (name, which))
+            if extra:
+                cmd += ["--timing_json", tj]
+            wall[which].append(gpu_step(cmd, a.step_timeout, env=env, cwd=tree))
+            written = sum(len(fs) for _, _, fs in os.walk(save))
+            assert written == (2 if is_y4m else 2 * n), (name, which, written)
+            if which == "long":
+                row["output_bytes_per_frame"] = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(save) for f in fs) // n
+                if extra:
+                    loops.append(json.load(open(tj)))
+            shutil.rmtree(save)
+            print("[bench_predict] %s %s %.1f s" % (name, which, wall[which][-1]), file=sys.stderr, flush=True)
+
+        # the runs of y4m and y4m_scene_cut alternate (same minutes, same neighbours on the box); every other setting runs on its own
+        groups = [[c] for c in configs if not c[0].startswith("y4m")] + ([[c for c in configs if c[0].startswith("y4m")]] if a.y4m else [])
+        for group in groups:
             for which, n, times in (("short", a.short, a.short_repeats), ("long", a.frames, a.repeats)):
                 for _ in range(times):
-                    save = os.path.join(tmp, "out_%s_%s" % (name, which))
-                    cmd = [sys.executable, "predict.py", "--dataset", "RLV", "--lowlight_images_path", roots[which], "--model_pretrain",
-                           weights, "--save", save, "--graph", "1", "--precision", "bf16"] + extra
-                    if name == "y4m":
-                        cmd.append(y4m_files[which])
-                    tj = os.path.join(tmp, "timing_%s_%s.json" % (name, which))
-                    if extra:
-                        cmd += ["--timing_json", tj]
-                    wall[which].append(gpu_step(cmd, a.step_timeout, env=env, cwd=tree))
-                    written = sum(len(fs) for _, _, fs in os.walk(save))
-                    assert written == (2 if name == "y4m" else 2 * n), (name, which, written)
-                    if which == "long":
-                        row["output_bytes_per_frame"] = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(save) for f in fs) // n
-                        if extra:
-                            loops.append(json.load(open(tj)))
-                    shutil.rmtree(save)
-                    print("[bench_predict] %s %s %.1f s" % (name, which, wall[which][-1]), file=sys.stderr, flush=True)
+                    for name, tree, extra in group:
+                        run_once(name, tree, extra, which, n)
+        for name, tree, extra in configs:
+            row, wall, loops = state[name]
             if loops:
                 fps = [l["fps"] for l in loops]
                 row["loop"] = sorted(loops, key=lambda l: l["fps"])[len(loops) // 2]          # the median run's split
@@ -285,6 +366,9 @@ def main():
                 row["fps_runs"] = [round(v, 2) for v in fps]
                 row["fps_median"] = round(statistics.median(fps), 2)
                 row["fps_spread"] = round(max(fps) - min(fps), 2)
+                if "scene_wait_ms" in lp:
+                    row["scene_wait_ms_runs"] = [round(l["scene_wait_ms"], 4) for l in loops]
+                    row["cuts_runs"] = [l["cuts"] for l in loops]
             row["wall_s"] = {k: [round(v, 2) for v in vs] for k, vs in wall.items()}
             row["differential_fps"] = round((a.frames - a.short) / (statistics.median(wall["long"]) - statistics.median(wall["short"])), 2)
             out["end_to_end"][name] = row

@@ -320,6 +320,32 @@ class Ops:
         self.lib.call("zt_rgb_f32_to_yuv", x, out, fmt.H, fmt.W, fmt.ss, fmt.siting, fmt.encode_coef(), self._s(x))
         return out
 
+    # ---- scene cuts (zt_scene.hip) ------------------------------------------------------------------------------
+    def luma_grid(self, payload, fmt, out=None):
+        """Y4M payload of `fmt` (1-D uint8), or its luma plane alone (H * W bytes, 1-D or [H,W]) -> int32 [ceil(H/16), ceil(W/16)]:
+        per 16 x 16 cell the sum of max(Y - yo, 0), yo = `fmt.decode_coef()[0]` (at most 65280, the library's uint32)."""
+        fmt.check()
+        n = fmt.H * fmt.W
+        assert payload.dtype == torch.uint8 and payload.is_contiguous() and \
+            ((payload.dim() == 1 and payload.numel() in (n, fmt.frame_bytes)) or tuple(payload.shape) == (fmt.H, fmt.W)), \
+            (payload.dtype, tuple(payload.shape), fmt.frame_bytes)
+        gh, gw = (fmt.H + 15) // 16, (fmt.W + 15) // 16
+        if out is None:
+            out = torch.empty((gh, gw), dtype=torch.int32, device=payload.device)
+        assert out.numel() == gh * gw and out.dtype == torch.int32 and out.is_contiguous() and out.device == payload.device
+        self.lib.call("zt_luma_grid_u8", payload, fmt.H, fmt.W, int(fmt.decode_coef()[0]), out, self._s(payload))
+        return out
+
+    def grid_sad(self, a, b, out=None):
+        """two grids of `luma_grid` (int32, same size) -> int64 [2]: sum |a - b|, sum (a + b); `out` is overwritten"""
+        assert a.dtype == torch.int32 and b.dtype == torch.int32 and a.is_contiguous() and b.is_contiguous() and \
+            a.numel() == b.numel() and a.device == b.device, (a.dtype, b.dtype, tuple(a.shape), tuple(b.shape))
+        if out is None:
+            out = torch.empty(2, dtype=torch.int64, device=a.device)
+        assert tuple(out.shape) == (2,) and out.dtype == torch.int64 and out.is_contiguous() and out.device == a.device
+        self.lib.call("zt_grid_sad_u32", a, b, a.numel(), out, self._s(a))
+        return out
+
     def psnr_u8(self, a, b):
         """evals.py:83-85: cv2.PSNR of round(a*255), round(b*255) -> python float (inf when identical); one 8-byte read-back."""
         _f32c(a), _f32c(b)
