@@ -334,6 +334,25 @@ int zt_yuv_to_planar_f32(const unsigned char* src, float* dst, int H, int W, int
                          zt_stream_t stream);
 int zt_rgb_f32_to_yuv(const float* src, unsigned char* dst, int H, int W, int ss, int siting, const int* coef, zt_stream_t stream);
 
+/* ---- high-bit-depth raw video frames (zt_yuv16.hip): planar Y'CbCr of depth B in {9, 10, 12, 14, 16} <-> RGB, DESIGN 8f ----------
+ * The payload has the plane shapes above as little-endian uint16, the value in the low B bits; a sample above m = 2^B - 1 is read
+ * as m.  ss, siting, the tap tables and the footprints are those of the 8-bit entry points.  coef: HOST pointer to 64-bit integers,
+ * round(c * 2^20) with matrix, range and depth folded in (zero-tig_amd/y4m.py); every entry must fit 32 bits.  mid = 2^(B-1).
+ *   decode: 6 values yo, CY, CRV, CGU, CGV, CBU; y = 16 CY (min(Y, m) - yo), u = U16 - 16 mid, v = V16 - 16 mid (chroma 16x as above),
+ *     R16 = clip16((y + CRV v + 2^23) >> 24), G16 = clip16((y - CGU u - CGV v + 2^23) >> 24), B16 = clip16((y + CBU u + 2^23) >> 24);
+ *     the value written is float(L16) / 65535.f.
+ *   encode: 10 values yo, CYR, CYG, CYB, CUR, CUG, CUB, CVR, CVG, CVB; L16 = x > 0 ? (x < 1 ? (int)(x * 65535.f + 0.5f) : 65535) : 0
+ *     (NaN -> 0); Y = yo + ((CYR R + CYG G + CYB B + 2^19) >> 20); U = mid + ((CUR Rs + CUG Gs + CUB Bs + 2^(19+sh)) >> (20+sh)), V
+ *     alike, over the footprint sums of the 16-bit levels; every plane clipped to 0..m.
+ * zt_luma_grid_u16: zt_luma_grid_u8 (below) of the plane min(y, m) >> (B - 8), bit for bit; yo8 is the 8-bit offset (16 or 0).
+ * With W % 8 == 0 (the grid: W % 16 == 0) and 16-byte aligned pointers every access is 8 or 16 bytes wide; otherwise 2-byte
+ * accesses, same result.  Any other depth, and the size / siting combinations the 8-bit entry points reject: ZT_EINVAL. */
+int zt_yuv16_to_planar_f32(const uint16_t* src, float* dst, int H, int W, int ss, int siting, int depth, const long long* coef,
+                           zt_stream_t stream);
+int zt_rgb_f32_to_yuv16(const float* src, uint16_t* dst, int H, int W, int ss, int siting, int depth, const long long* coef,
+                        zt_stream_t stream);
+int zt_luma_grid_u16(const uint16_t* y, int H, int W, int depth, int yo8, unsigned int* grid /* [gh*gw] */, zt_stream_t stream);
+
 /* ---- scene cuts in a raw video stream (zt_scene.hip): predict.py --y4m_scene_cut, zero-tig_amd/scenecut.py, DESIGN 8e ------------
  * zt_luma_grid_u8: the luma plane y [H][W] (the first H * W bytes of a payload) in 16 x 16 cells, gh = ceil(H / 16) rows of
  *   gw = ceil(W / 16), edge cells holding the pixels that exist: grid[i * gw + j] = sum over the cell of max(y - yo, 0), at most

@@ -39,12 +39,15 @@ parser.add_argument("--timing_json", type=str, default=None,
                     help="write the loop's host-side time split (decode wait, step, copy wait, writer wait) to this file")
 parser.add_argument("--y4m_in", type=str, default=None,
                     help="raw video in: a YUV4MPEG2 file, or - for standard input (8-bit C420jpeg / C420mpeg2 / C420paldv / C420 / C422 / "
-                         "C444, progressive); replaces the dataset walk, one stream is one sequence; needs --graph 1.  The results "
+                         "C444, or 9, 10, 12, 14 or 16 bits per sample as C420pN / C422pN / C444pN; progressive); replaces the dataset walk, one stream is one sequence; needs --graph 1.  The results "
                          "are written as <save>/<stem>_enhance.y4m and <stem>_denoise.y4m in the input's own layout")
 parser.add_argument("--y4m_out", type=str, default=None,
                     help="write the enhance stream here instead (and no denoise stream); - is standard output, every log line then goes to stderr")
 parser.add_argument("--y4m_resize", type=int, default=0, choices=[0, 1],
                     help="0: enhance at the stream's own size; 1: the loaders' resize((1920, 1080)) first, the output streams are 1920x1080")
+parser.add_argument("--y4m_out_depth", type=int, default=0, choices=[0, 8, 9, 10, 12, 14, 16],
+                    help="bits per sample of the output streams; 0: as the input.  An 8-bit stream can leave as 10-bit (the model's fp32 "
+                         "result keeps its gradation) and a deep one as 8-bit; needs --y4m_in")
 parser.add_argument("--y4m_matrix", type=str, default="bt709", choices=["bt709", "bt601"],
                     help="the Y'CbCr matrix of the stream (Y4M cannot carry it)")
 parser.add_argument("--y4m_scene_cut", type=float, default=0.0,
@@ -78,14 +81,21 @@ def main_y4m(args):
     reader = y4m.Y4MReader(args.y4m_in)
     head = reader.header
     fmt = head.format(args.y4m_matrix)
-    print("Y4M input: %dx%d C%s %s %s" % (head.W, head.H, head.ctag, "full" if head.full else "limited", args.y4m_matrix))
+    if fmt.depth > 8 and args.y4m_resize:
+        reader.close()
+        parser.error("--y4m_resize 1 cannot be combined with a %d-bit --y4m_in stream (C%s): the resize is 8-bit" % (fmt.depth, head.ctag))
+    print("Y4M input: %dx%d C%s %d-bit %s %s" % (head.W, head.H, head.ctag, fmt.depth, "full" if head.full else "limited", args.y4m_matrix))
+    out_depth = args.y4m_out_depth or fmt.depth
+    if out_depth > 8 and fmt.depth == 8 and fmt.ss != 444 and fmt.siting == 0:
+        logging.info("C%s -> C%s: the conversion keeps the centre siting of the input, which the output tag cannot express",
+                     head.ctag, y4m.ctag_at_depth(head.ctag, out_depth))
     model = Finetunemodel(args).to(dev)
     model.eval()
     for p in model.parameters():
         p.requires_grad = False
     step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080) if args.y4m_resize else None,
-                                                                   yuv=fmt)
-    out_head = head.resized(step.yuv_format.W, step.yuv_format.H)
+                                                                   yuv=fmt, yuv_out_depth=out_depth)
+    out_head = head.resized(step.yuv_format.W, step.yuv_format.H)._replace(ctag=y4m.ctag_at_depth(head.ctag, out_depth))
     det, cuts, scores, rels = None, [], [], []
     if args.y4m_scene_cut > 0:
         det = importlib.import_module("zero-tig_amd.scenecut").SceneCut(
@@ -163,6 +173,8 @@ def main():
     args = parser.parse_args()
     if args.y4m_in is None and (args.y4m_out is not None or args.y4m_resize):
         parser.error("--y4m_out / --y4m_resize need --y4m_in")
+    if args.y4m_out_depth and args.y4m_in is None:
+        parser.error("--y4m_out_depth needs --y4m_in")
     if args.y4m_scene_cut < 0:
         parser.error("--y4m_scene_cut is a threshold in [0, 1], 0 = off; got %g" % args.y4m_scene_cut)
     if args.y4m_scene_cut > 0 and args.y4m_in is None:

@@ -20,6 +20,8 @@
     zero-tig_amd/y4m.py (C420mpeg2, limited range, bt709), form one Y4M file; `y4m` in "end_to_end" is predict.py --graph 1
     --precision bf16 --y4m_in over it (two Y4M streams written), measured like the PNG settings, and "convert" holds the three
     conversions alone at 1080p: HIP-event median over --reps calls, the bytes each moves and the share of the HBM peak.
+    --y4m-depth B (9 .. 16): the same loop over the clip as C420pB as "y4m_pB", its runs alternating with those of "y4m", and the
+    two deep conversions (zt_yuv16.hip) next to the 8-bit ones in "convert".
     --scene-cut T [T ..]: the same loop with predict.py --y4m_scene_cut T as "y4m_scene_cut_T", its runs alternating with those of
     "y4m" (flag off), with the time the loop was blocked for the detector (scene_wait_ms) and the sequences restarted (cuts); "scene"
     holds the two kernels of zt_scene.hip alone.
@@ -30,7 +32,9 @@ Usage: python tools/bench_predict.py [--parent DIR] [--frames 64] [--short 16] [
        python tools/bench_predict.py --skip-encode --frames 256 --short 64 --settings 1 2 --out profiles/predict_png_1080p_256.json
        python tools/bench_predict.py --skip-encode --y4m --frames 256 --short 64 --settings 1 --out profiles/predict_y4m_1080p.json
        python tools/bench_predict.py --skip-encode --y4m --scene-cut 0.5 0.03 --frames 256 --short 64 --settings \
-                                     --out profiles/predict_y4m_scene_cut_1080p.json"""
+                                     --out profiles/predict_y4m_scene_cut_1080p.json
+       python tools/bench_predict.py --skip-encode --y4m --y4m-depth 10 --frames 256 --short 64 --settings \
+                                     --out profiles/predict_y4m_deep_1080p.json"""
 import argparse
 import importlib
 import json
@@ -116,6 +120,14 @@ def convert_mode(a):
              "yuv_to_planar_f32": (lambda: ops.yuv_to_planar_f32(payload, fmt, out=x), fmt.frame_bytes + 12 * H * W),
              "rgb_f32_to_yuv": (lambda: ops.rgb_f32_to_yuv(x, fmt, out=back), fmt.frame_bytes + 12 * H * W)}
     out = {"format": "1080x1920 C420mpeg2 limited bt709", "payload_bytes": fmt.frame_bytes}
+    if a.y4m_depth > 8:                             # the two deep conversions next to the 8-bit ones, same frame, same session
+        deep = fmt._replace(depth=a.y4m_depth)
+        payload16 = torch.from_numpy(y4m.encode_host(rgb.astype(np.uint16) * 257, deep)).cuda()
+        back16 = torch.empty_like(payload16)
+        calls["yuv16_to_planar_f32"] = (lambda: ops.yuv_to_planar_f32(payload16, deep, out=x), deep.frame_bytes + 12 * H * W)
+        calls["rgb_f32_to_yuv16"] = (lambda: ops.rgb_f32_to_yuv(x, deep, out=back16), deep.frame_bytes + 12 * H * W)
+        out["deep_format"] = "1080x1920 C420p%d limited bt709" % a.y4m_depth
+        out["deep_payload_bytes"] = deep.frame_bytes
     for name, (fn, moved) in calls.items():
         for _ in range(5):
             fn()
@@ -184,19 +196,21 @@ def scene_mode(a):
         json.dump(out, fh)
 
 
-def make_y4m(tmp, roots, frames, short, distinct):
-    """the PNG clip's pixels as Y4M files (host encoder; the `distinct` frames encoded once, written round-robin)"""
+def make_y4m(tmp, roots, frames, short, distinct, depth=8):
+    """the PNG clip's pixels as Y4M files (host encoder; the `distinct` frames encoded once, written round-robin); depth > 8: as
+    C420pN, from the same pixels as 16-bit levels (x 257)"""
     import numpy as np
     from PIL import Image
     sys.path.insert(0, ROOT)
     y4m = importlib.import_module("zero-tig_amd.y4m")
-    head = y4m.Header(1920, 1080, "30:1", "p", None, "420mpeg2", "LIMITED")
+    head = y4m.Header(1920, 1080, "30:1", "p", None, "420mpeg2" if depth == 8 else "420p%d" % depth, "LIMITED")
     fmt = head.format("bt709")
     d = os.path.join(roots["long"], "input", "S01", "low_light_10")
-    pay = [y4m.encode_host(np.asarray(Image.open(os.path.join(d, "%05d.png" % (i + 1)))), fmt) for i in range(min(distinct, frames))]
+    rgb = [np.asarray(Image.open(os.path.join(d, "%05d.png" % (i + 1)))) for i in range(min(distinct, frames))]
+    pay = [y4m.encode_host(p if depth == 8 else p.astype(np.uint16) * 257, fmt) for p in rgb]
     files = {}
     for name, n in (("long", frames), ("short", short)):
-        files[name] = os.path.join(tmp, "clip_%s.y4m" % name)
+        files[name] = os.path.join(tmp, "clip%s_%s.y4m" % ("" if depth == 8 else "_p%d" % depth, name))
         y4m.write_file(files[name], head, [pay[i % len(pay)] for i in range(n)])
     return files, fmt.frame_bytes
 
@@ -256,6 +270,9 @@ def main():
     ap.add_argument("--sizes", type=str, nargs="+", default=["1080x1920", "2160x3840"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--parent", type=str, default=None, help="checkout of the parent commit (runs against this tree's library)")
+    ap.add_argument("--y4m-depth", type=int, default=8, choices=[8, 9, 10, 12, 14, 16],
+                    help="with --y4m, B > 8: also the Y4M loop over the same clip as C420pB (setting y4m_pB, its runs alternating with "
+                         "those of y4m), and the two deep conversions in convert")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--short", type=int, default=16)
     ap.add_argument("--settings", type=int, nargs="*", default=[0, 1, 2], choices=[0, 1, 2],
@@ -304,7 +321,8 @@ def main():
             out["encode"] = json.load(open(ej))
         if a.y4m:
             cj = os.path.join(tmp, "convert.json")
-            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "convert", "--json", cj, "--reps", str(a.reps)], a.step_timeout)
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "convert", "--json", cj, "--reps", str(a.reps), "--y4m-depth",
+                      str(a.y4m_depth)], a.step_timeout)
             out["convert"] = json.load(open(cj))
         if a.y4m and a.scene_cut:
             sj = os.path.join(tmp, "scene.json")
@@ -315,11 +333,18 @@ def main():
                             "Ops.luma_grid (16-byte and byte loads) and Ops.grid_sad alone, HIP-event median of %d calls" % a.reps)
         roots, weights = make_clip(tmp, a.frames, a.short, a.distinct)
         y4m_files = make_y4m(tmp, roots, a.frames, a.short, a.distinct)[0] if a.y4m else None
+        deep_name = "y4m_p%d" % a.y4m_depth
+        deep_files = make_y4m(tmp, roots, a.frames, a.short, a.distinct, a.y4m_depth)[0] if a.y4m and a.y4m_depth > 8 else None
         so = os.path.join(ROOT, "zero-tig_amd", "libzerotig_hip.so")
         configs = ([("parent", a.parent, [])] if a.parent else []) + [("device_png_%d" % v, ROOT, ["--device_png", str(v)])
                                                                       for v in a.settings]
         if a.y4m:
             configs.append(("y4m", ROOT, ["--y4m_in"]))
+            if deep_files:
+                configs.append((deep_name, ROOT, ["--y4m_in"]))
+                out["what"] += ("; %s = the y4m loop over the same pixels as C420p%d (16-bit levels = 257 x the PNG's), streams written at "
+                                "that depth, its runs alternating with those of y4m; convert.yuv16_to_planar_f32 / rgb_f32_to_yuv16 = "
+                                "the deep conversions" % (deep_name, a.y4m_depth))
             for T in a.scene_cut:
                 configs.append(("y4m_scene_cut_%g" % T, ROOT, ["--y4m_scene_cut", str(T), "--y4m_in"]))
         out["end_to_end"] = {}
@@ -333,7 +358,7 @@ def main():
             cmd = [sys.executable, "predict.py", "--dataset", "RLV", "--lowlight_images_path", roots[which], "--model_pretrain",
                    weights, "--save", save, "--graph", "1", "--precision", "bf16"] + extra
             if is_y4m:
-                cmd.append(y4m_files[which])
+                cmd.append((deep_files if name == deep_name else y4m_files)[which])
             tj = os.path.join(tmp, "timing_%s_%s.json" % (name, which))
             if extra:
                 cmd += ["--timing_json", tj]

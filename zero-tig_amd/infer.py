@@ -36,20 +36,28 @@ class InferStep:
     straight into the input when `ingest_size` is None or (W, H), `Ops.yuv_to_rgb_u8` + `Ops.ingest_u8` otherwise -- and
     `step.yuv = (enhance_payload, denoise_payload)` holds the two results as payloads of the SAME subsampling, siting, matrix and
     range at the output size (`step.yuv_format`), made from H2 / H3 by `Ops.rgb_f32_to_yuv`.  All of it is part of the captured
-    graph; `step.u8` / `step.png` are filled as without it.
+    graph; `step.u8` / `step.png` are filled as without it.  `yuv_out_depth` (None = the input's) sets the depth of the two output
+    payloads alone: an 8-bit stream can leave as 10-bit and the other way round; which conversion runs is decided here, at
+    construction, so the captured graph has no branch.  A deep input (depth > 8) is never resized: `ingest_size` other than None
+    or (W, H) raises ValueError.
 
     Weights are prepared again when a parameter or BatchNorm buffer changed (`_version` / `data_ptr()` of the tensors, e.g. after
     `load_state_dict`); the prepared buffers keep their addresses, so a captured graph stays valid across a reload."""
 
-    def __init__(self, model, use_graph=True, ingest_size=(1920, 1080), png=False, yuv=None):
+    def __init__(self, model, use_graph=True, ingest_size=(1920, 1080), png=False, yuv=None, yuv_out_depth=None):
         assert int(png) in (0, 1, 2), png
         self.model, self.use_graph, self.ingest_size, self.want_png = model, use_graph, ingest_size, int(png)
         self.graph, self.x, self.out, self.u8, self.png = None, None, None, None, None
         self.fmt, self.yuv, self.yuv_format, self.loaded, self._payload = yuv, None, None, None, None
+        assert yuv is not None or yuv_out_depth is None, "yuv_out_depth needs yuv="
         if yuv is not None:
             yuv.check()
             W, H = (yuv.W, yuv.H) if ingest_size is None else ingest_size
-            self.yuv_format = yuv.resized(W, H).check()          # the output streams: same layout at the output size
+            if yuv.depth > 8 and (W, H) != (yuv.W, yuv.H):
+                raise ValueError("InferStep: a %d-bit input cannot be resized (%dx%d -> %dx%d): the resize is 8-bit; use ingest_size=None"
+                                 % (yuv.depth, yuv.W, yuv.H, W, H))
+            # the output streams: same layout at the output size, at the input's depth unless another is asked for
+            self.yuv_format = yuv.resized(W, H)._replace(depth=yuv.depth if yuv_out_depth is None else int(yuv_out_depth)).check()
         self.n_eager_steady, self.n_captures, self.n_prepares = 0, 0, 0
         self._wp, self._wsig, self._bound = None, None, None
 

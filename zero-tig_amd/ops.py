@@ -288,8 +288,10 @@ class Ops:
 
     def yuv_to_rgb_u8(self, payload, fmt, out=None):
         """Y4M payload (1-D uint8: planes Y, U, V of `fmt`, a `y4m.YuvFormat`) -> uint8 [H,W,3] RGB on the device: chroma
-        upsampled for the format's siting and the integer matrix of DESIGN 8d, bit-exact."""
+        upsampled for the format's siting and the integer matrix of DESIGN 8d, bit-exact.  8-bit formats only."""
         self._yuv_payload(payload, fmt)
+        if fmt.depth > 8:
+            raise ValueError("yuv_to_rgb_u8: a %d-bit format has no 8-bit RGB decode (yuv_to_planar_f32 takes it)" % fmt.depth)
         if out is None:
             out = torch.empty((fmt.H, fmt.W, 3), dtype=torch.uint8, device=payload.device)
         assert tuple(out.shape) == (fmt.H, fmt.W, 3) and out.dtype == torch.uint8 and out.is_contiguous()
@@ -298,41 +300,53 @@ class Ops:
 
     def yuv_to_planar_f32(self, payload, fmt, out=None):
         """Y4M payload -> fp32 [1,3,H,W] in [0,1]: `ingest_u8(yuv_to_rgb_u8(payload), size=None)` bit for bit in one pass (no RGB
-        intermediate, any H * W)."""
+        intermediate, any H * W).  A deep format (depth > 8): 16-bit levels / 65535 by the definition of DESIGN 8f."""
         self._yuv_payload(payload, fmt)
         dev = payload.device
         if out is None:
             out = torch.empty((1, 3, fmt.H, fmt.W), dtype=torch.float32, device=dev)
         assert tuple(out.shape) == (1, 3, fmt.H, fmt.W) and out.dtype == torch.float32 and out.is_contiguous()
+        if fmt.depth > 8:
+            self.lib.call("zt_yuv16_to_planar_f32", payload, out, fmt.H, fmt.W, fmt.ss, fmt.siting, fmt.depth, fmt.decode_coef(),
+                          self._s(payload))
+            return out
         self.lib.call("zt_yuv_to_planar_f32", payload, out, fmt.H, fmt.W, fmt.ss, fmt.siting, fmt.decode_coef(),
                       self._to_tensor_lut(dev), self._s(payload))
         return out
 
     def rgb_f32_to_yuv(self, x, fmt, out=None):
         """[1,3,H,W] fp32 in [0,1] -> Y4M payload (1-D uint8) of `fmt`: the levels `quantize_u8(x, 0)` makes (predict.py's
-        truncation), converted and chroma-subsampled in the same pass."""
+        truncation), converted and chroma-subsampled in the same pass.  A deep format (depth > 8): from the 16-bit levels
+        (int)(x * 65535 + 0.5) of DESIGN 8f; the payload is still 1-D uint8, `fmt.frame_bytes` long."""
         _f32c(x)
         fmt.check()
         assert tuple(x.shape) == (1, 3, fmt.H, fmt.W), (tuple(x.shape), fmt)
         if out is None:
             out = torch.empty(fmt.frame_bytes, dtype=torch.uint8, device=x.device)
         assert out.dtype == torch.uint8 and out.dim() == 1 and out.numel() == fmt.frame_bytes and out.is_contiguous()
+        if fmt.depth > 8:
+            self.lib.call("zt_rgb_f32_to_yuv16", x, out, fmt.H, fmt.W, fmt.ss, fmt.siting, fmt.depth, fmt.encode_coef(), self._s(x))
+            return out
         self.lib.call("zt_rgb_f32_to_yuv", x, out, fmt.H, fmt.W, fmt.ss, fmt.siting, fmt.encode_coef(), self._s(x))
         return out
 
     # ---- scene cuts (zt_scene.hip) ------------------------------------------------------------------------------
     def luma_grid(self, payload, fmt, out=None):
         """Y4M payload of `fmt` (1-D uint8), or its luma plane alone (H * W bytes, 1-D or [H,W]) -> int32 [ceil(H/16), ceil(W/16)]:
-        per 16 x 16 cell the sum of max(Y - yo, 0), yo = `fmt.decode_coef()[0]` (at most 65280, the library's uint32)."""
+        per 16 x 16 cell the sum of max(Y - yo, 0), yo = `fmt.decode_coef()[0]` (at most 65280, the library's uint32).
+        A deep format (the luma plane is then 2 * H * W bytes): the same grid over min(Y, m) >> (depth - 8), yo = 16 or 0."""
         fmt.check()
-        n = fmt.H * fmt.W
+        n = fmt.H * fmt.W * (2 if fmt.depth > 8 else 1)
         assert payload.dtype == torch.uint8 and payload.is_contiguous() and \
-            ((payload.dim() == 1 and payload.numel() in (n, fmt.frame_bytes)) or tuple(payload.shape) == (fmt.H, fmt.W)), \
+            ((payload.dim() == 1 and payload.numel() in (n, fmt.frame_bytes)) or tuple(payload.shape) == (fmt.H, n // fmt.H)), \
             (payload.dtype, tuple(payload.shape), fmt.frame_bytes)
         gh, gw = (fmt.H + 15) // 16, (fmt.W + 15) // 16
         if out is None:
             out = torch.empty((gh, gw), dtype=torch.int32, device=payload.device)
         assert out.numel() == gh * gw and out.dtype == torch.int32 and out.is_contiguous() and out.device == payload.device
+        if fmt.depth > 8:
+            self.lib.call("zt_luma_grid_u16", payload, fmt.H, fmt.W, fmt.depth, 0 if fmt.full else 16, out, self._s(payload))
+            return out
         self.lib.call("zt_luma_grid_u8", payload, fmt.H, fmt.W, int(fmt.decode_coef()[0]), out, self._s(payload))
         return out
 

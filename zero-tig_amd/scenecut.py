@@ -5,7 +5,8 @@ its own; `pop` waits for the detector's event, never for the device or the step'
 loop that event still completes about a frame late, so the host stops running ahead of the device and the loop loses 4 %.)
 
 The score.  The luma plane is cut into 16 x 16 cells (edge cells hold the pixels that exist); G[i][j] = sum over the cell of
-max(Y - yo, 0), yo = 16 for limited range and 0 for full range (`Ops.luma_grid`).  For a pair of frames sad = sum |G_n - G_(n-1)|
+max(Y - yo, 0), yo = 16 for limited range and 0 for full range (`Ops.luma_grid`; a deep stream's luma is first cut to its top 8
+bits, so a threshold means the same at every depth).  For a pair of frames sad = sum |G_n - G_(n-1)|
 and tot = sum (G_n + G_(n-1)), 64-bit integers (`Ops.grid_sad`).  On the host rel_n = sad / max(tot, 1), rel_0 = 0,
 score_n = min(rel_n, |rel_n - rel_(n-1)|), and frame n starts a sequence when score_n > threshold; frame 0 always does."""
 import time
@@ -43,7 +44,7 @@ class SceneCut:
     def __init__(self, ops, dev, fmt, threshold):
         fmt.check()
         self.ops, self.dev, self.fmt, self.rule = ops, torch.device(dev), fmt, CutRule(threshold)
-        self._n = fmt.H * fmt.W
+        self._n = fmt.H * fmt.W * (2 if fmt.depth > 8 else 1)      # the luma plane's bytes
         cells = ((fmt.H + 15) // 16) * ((fmt.W + 15) // 16)
         self._cuda = self.dev.type == "cuda"
         self._stream = torch.cuda.Stream(self.dev) if self._cuda else None

@@ -2,11 +2,13 @@
 the kernels of csrc/zt_yuv.hip consume.
 
 A Y4M stream is one text line (`YUV4MPEG2 W.. H.. F..:.. I. A..:.. C... X...`) followed, per frame, by a `FRAME` line and the
-payload: plane Y [H][W], then U, then V, 8 bits each.  Video tools read and write it through pipes
+payload: plane Y [H][W], then U, then V, 8 bits each (or 16 bits little-endian with the value in the low 9, 10, 12, 14 or 16 bits:
+tags C420p10 ... C444p16).  Video tools read and write it through pipes
 (`ffmpeg -i in.mp4 -f yuv4mpegpipe - | predict.py --y4m_in - --y4m_out - | ffmpeg -i - out.mp4`), so no decoder lives here.
 
 `parse_header` -> `Header`; `Header.format(matrix)` -> `YuvFormat`, which fixes the conversion (subsampling, chroma siting, matrix,
-range) and carries the coefficient tables: round(c * 2^14) of the values derived from (Kr, Kb) in double precision.
+range, depth) and carries the coefficient tables: round(c * 2^14) of the values derived from (Kr, Kb) in double precision (DESIGN 8d);
+round(c * 2^20), int64, for the 16-bit levels of a deep format (csrc/zt_yuv16.hip).
 `Y4MReader` is an iterator over payloads: one thread reads the stream into a bounded ring of (pinned) buffers, so the loop's
 `next()` is a queue pop.  `Y4MWriter` follows `pngwriter.PngWriter`: a ring of pinned buffers, an asynchronous copy on the step's
 stream plus an event per frame, a bounded queue, ONE thread per stream (frames land in order), `close()` drains and re-raises.
@@ -22,21 +24,42 @@ import numpy as np
 import torch
 
 S = 14                                              # coefficient precision of the kernels
+S16 = 20                                            # the same for the deep formats (depth > 8)
+DEPTHS = (8, 9, 10, 12, 14, 16)
 KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 # C tag -> (subsampling, siting): 0 = chroma centred between its two luma columns, 1 = co-sited with the left one
 CTAGS = {"420jpeg": (420, 0), "420mpeg2": (420, 1), "420paldv": (420, 1), "420": (420, 1), "422": (422, 1), "444": (444, 0)}
+# the deep tags have no siting variants: left for 420 / 422, as the bare C420
+DEEP_CTAGS = {"%dp%d" % (ss, d): (ss, 0 if ss == 444 else 1, d) for ss in (420, 422, 444) for d in DEPTHS[1:]}
+
+
+def ctag_info(ctag):
+    """C tag -> (subsampling, siting, depth)"""
+    return DEEP_CTAGS[ctag] if ctag in DEEP_CTAGS else CTAGS[ctag] + (8,)
+
+
+def ctag_at_depth(ctag, depth):
+    """the tag of the same subsampling at another depth: a deep tag carries no siting, so an 8-bit 420 tag maps to 420pN, and
+    420pN maps back to 420mpeg2 (left siting, what the deep tag meant); at an unchanged depth the tag itself"""
+    ss, _, d = ctag_info(ctag)
+    if depth == d:
+        return ctag
+    return "%dp%d" % (ss, depth) if depth > 8 else {420: "420mpeg2", 422: "422", 444: "444"}[ss]
 
 
 def _q(v):
     return int(round(v * (1 << S)))
 
 
-class YuvFormat(collections.namedtuple("YuvFormat", "W H ss siting matrix full")):
-    """One 8-bit planar Y'CbCr frame layout and its conversion: ss in (420, 422, 444), siting 0 centre / 1 left, matrix "bt601" /
-    "bt709", full 0 (Y 16-235, chroma 16-240) / 1."""
+class YuvFormat(collections.namedtuple("YuvFormat", "W H ss siting matrix full depth", defaults=(8,))):
+    """One planar Y'CbCr frame layout and its conversion: ss in (420, 422, 444), siting 0 centre / 1 left, matrix "bt601" /
+    "bt709", full 0 (Y 16-235, chroma 16-240, times 2^(depth - 8)) / 1, depth 8 (one byte per sample) or 9, 10, 12, 14, 16 (uint16
+    little-endian, the value in the low `depth` bits)."""
     __slots__ = ()
 
     def check(self):
+        if self.depth not in DEPTHS:
+            raise ValueError("yuv format: depth %r is not one of %s" % (self.depth, ", ".join(str(d) for d in DEPTHS)))
         if self.ss not in (420, 422, 444) or self.siting not in (0, 1) or (self.ss == 444 and self.siting != 0):
             raise ValueError("yuv format: subsampling %r with siting %r is not supported" % (self.ss, self.siting))
         if self.matrix not in KR_KB:
@@ -52,26 +75,30 @@ class YuvFormat(collections.namedtuple("YuvFormat", "W H ss siting matrix full")
     @property
     def frame_bytes(self):
         hc, wc = self.chroma_shape
-        return self.H * self.W + 2 * hc * wc
+        return (self.H * self.W + 2 * hc * wc) * (2 if self.depth > 8 else 1)
 
     def resized(self, W, H):
         return self._replace(W=int(W), H=int(H))
 
     def planes(self, payload):
-        """numpy views (Y, U, V) of a payload (any 1-D uint8 array-like)"""
+        """numpy views (Y, U, V) of a payload (any 1-D uint8 array-like); uint16 views for depth > 8"""
         p = np.asarray(payload).reshape(-1)
         assert p.dtype == np.uint8 and p.size == self.frame_bytes, (p.dtype, p.size, self.frame_bytes)
+        if self.depth > 8:
+            p = p.view("<u2")
         hc, wc = self.chroma_shape
         n = self.H * self.W
         return p[:n].reshape(self.H, self.W), p[n:n + hc * wc].reshape(hc, wc), p[n + hc * wc:].reshape(hc, wc)
 
     def decode_coef(self):
-        """int32 [6] on the host: yo, CY, CRV, CGU, CGV, CBU (zt_yuv_to_rgb_u8 / zt_yuv_to_planar_f32)"""
-        return _coef(self.matrix, self.full)[0]
+        """int32 [6] on the host: yo, CY, CRV, CGU, CGV, CBU (zt_yuv_to_rgb_u8 / zt_yuv_to_planar_f32); for depth > 8 the int64
+        table of zt_yuv16_to_planar_f32"""
+        return (_coef16(self.matrix, self.full, self.depth) if self.depth > 8 else _coef(self.matrix, self.full))[0]
 
     def encode_coef(self):
-        """int32 [10] on the host: yo, CYR, CYG, CYB, CUR, CUG, CUB, CVR, CVG, CVB (zt_rgb_f32_to_yuv)"""
-        return _coef(self.matrix, self.full)[1]
+        """int32 [10] on the host: yo, CYR, CYG, CYB, CUR, CUG, CUB, CVR, CVG, CVB (zt_rgb_f32_to_yuv); for depth > 8 the int64
+        table of zt_rgb_f32_to_yuv16"""
+        return (_coef16(self.matrix, self.full, self.depth) if self.depth > 8 else _coef(self.matrix, self.full))[1]
 
 
 _COEF = {}
@@ -92,10 +119,35 @@ def _coef(matrix, full):
     return _COEF[key]
 
 
+def _coef16(matrix, full, depth):
+    """the tables of DESIGN 8f: 16-bit RGB levels against samples of `depth` bits, round(c * 2^20), int64"""
+    key = (matrix, int(bool(full)), int(depth))
+    if key not in _COEF:
+        kr, kb = KR_KB[matrix]
+        kg = 1.0 - kr - kb
+        k = 1 << (depth - 8)
+        yo, yr, cr = (0, (1 << depth) - 1, (1 << depth) - 1) if full else (16 * k, 219 * k, 224 * k)
+
+        def q(v):
+            return int(round(v * (1 << S16)))
+        cy, cs = 65535.0 / yr, 65535.0 / cr
+        dec = [yo, q(cy), q(cs * 2 * (1 - kr)), q(cs * 2 * kb * (1 - kb) / kg), q(cs * 2 * kr * (1 - kr) / kg), q(cs * 2 * (1 - kb))]
+        cyr, cyb = q(kr * yr / 65535.0), q(kb * yr / 65535.0)
+        cur, cub = q(-kr / (2 * (1 - kb)) * cr / 65535.0), q(0.5 * cr / 65535.0)
+        cvr, cvb = q(0.5 * cr / 65535.0), q(-kb / (2 * (1 - kr)) * cr / 65535.0)
+        enc = [yo, cyr, q(yr / 65535.0) - cyr - cyb, cyb, cur, -(cur + cub), cub, cvr, -(cvr + cvb), cvb]
+        _COEF[key] = (torch.tensor(dec, dtype=torch.int64), torch.tensor(enc, dtype=torch.int64))
+    return _COEF[key]
+
+
 def encode_host(rgb, fmt):
     """uint8 [H][W][3] -> payload (numpy): the encode of zt_rgb_f32_to_yuv on the host, in int64, from the same coefficient table.
-    For tools that have to make a stream without a device; tests/test_y4m.py restates the definition on its own."""
+    A deep format (depth > 8) takes uint16 [H][W][3], 16-bit levels, and gives the encode of zt_rgb_f32_to_yuv16.
+    For tools that have to make a stream without a device; tests/test_y4m.py and test_y4m_deep.py restate the definitions on their own."""
     yo, cyr, cyg, cyb, cur, cug, cub, cvr, cvg, cvb = (int(v) for v in fmt.check().encode_coef())
+    deep = fmt.depth > 8
+    assert np.asarray(rgb).dtype == (np.uint16 if deep else np.uint8), (np.asarray(rgb).dtype, fmt.depth)
+    S, mid, top, dtype = (S16, 1 << (fmt.depth - 1), (1 << fmt.depth) - 1, "<u2") if deep else (14, 128, 255, np.uint8)
     R, G, B = (np.asarray(rgb)[..., i].astype(np.int64) for i in range(3))
     Y = yo + ((cyr * R + cyg * G + cyb * B + (1 << (S - 1))) >> S)
 
@@ -109,9 +161,9 @@ def encode_host(rgb, fmt):
         return s[0::2] + s[1::2] if fmt.ss == 420 else s
     sh = (0 if fmt.ss == 444 else 1 if fmt.siting == 0 else 2) + (1 if fmt.ss == 420 else 0)
     Rs, Gs, Bs = foot(R), foot(G), foot(B)
-    U = 128 + ((cur * Rs + cug * Gs + cub * Bs + (1 << (S - 1 + sh))) >> (S + sh))
-    V = 128 + ((cvr * Rs + cvg * Gs + cvb * Bs + (1 << (S - 1 + sh))) >> (S + sh))
-    return np.concatenate([np.clip(p, 0, 255).astype(np.uint8).reshape(-1) for p in (Y, U, V)])
+    U = mid + ((cur * Rs + cug * Gs + cub * Bs + (1 << (S - 1 + sh))) >> (S + sh))
+    V = mid + ((cvr * Rs + cvg * Gs + cvb * Bs + (1 << (S - 1 + sh))) >> (S + sh))
+    return np.concatenate([np.clip(p, 0, top).astype(dtype).reshape(-1) for p in (Y, U, V)]).view(np.uint8)
 
 
 # ---- the container ----------------------------------------------------------------------------------------------------------------
@@ -119,8 +171,8 @@ MAGIC = b"YUV4MPEG2"
 
 
 class Header(collections.namedtuple("Header", "W H fps interlace aspect ctag color_range")):
-    """fps / aspect: "num:den" strings or None; interlace: "p", "?" or None; ctag: a key of CTAGS ("420" when the stream has no C
-    parameter); color_range: the XCOLORRANGE value ("FULL", "LIMITED") or None."""
+    """fps / aspect: "num:den" strings or None; interlace: "p", "?" or None; ctag: a key of CTAGS or DEEP_CTAGS ("420" when the
+    stream has no C parameter); color_range: the XCOLORRANGE value ("FULL", "LIMITED") or None."""
     __slots__ = ()
 
     @property
@@ -128,8 +180,8 @@ class Header(collections.namedtuple("Header", "W H fps interlace aspect ctag col
         return int(self.color_range == "FULL")
 
     def format(self, matrix="bt709"):
-        ss, siting = CTAGS[self.ctag]
-        return YuvFormat(self.W, self.H, ss, siting, matrix, self.full).check()
+        ss, siting, depth = ctag_info(self.ctag)
+        return YuvFormat(self.W, self.H, ss, siting, matrix, self.full, depth).check()
 
     def resized(self, W, H):
         return self._replace(W=int(W), H=int(H))
@@ -148,8 +200,9 @@ class Header(collections.namedtuple("Header", "W H fps interlace aspect ctag col
         return (" ".join(parts) + "\n").encode("ascii")
 
 
-def parse_header(line):
-    """The stream's first line (bytes, with or without the newline) -> Header.  Raises ValueError naming the field it rejects."""
+def parse_header(line, max_depth=8):
+    """The stream's first line (bytes, with or without the newline) -> Header.  Raises ValueError naming the field it rejects.
+    `max_depth`: the deepest sample a caller takes; 8 rejects the deep tags (C420p10 ...), 16 accepts every one of DEEP_CTAGS."""
     try:
         text = bytes(line).decode("ascii").rstrip("\n")
     except UnicodeDecodeError:
@@ -175,13 +228,14 @@ def parse_header(line):
     if f["I"] not in (None, "p", "?"):
         raise ValueError("y4m: field I%s: interlaced streams are not supported (Ip or I? only)" % f["I"])
     ctag = "420" if f["C"] is None else f["C"]
-    if ctag not in CTAGS:
+    if ctag not in CTAGS and not (ctag in DEEP_CTAGS and DEEP_CTAGS[ctag][2] <= max_depth):
         why = ("more than 8 bits per sample" if re.search(r"p\d+$", ctag) or ctag == "mono16" else
                "no chroma planes" if ctag.startswith("mono") else "an alpha plane" if "alpha" in ctag else "unknown layout")
-        raise ValueError("y4m: field C%s is not supported (%s); one of %s" % (ctag, why, ", ".join("C" + c for c in CTAGS)))
+        deep = [c for c, v in DEEP_CTAGS.items() if v[2] <= max_depth]
+        raise ValueError("y4m: field C%s is not supported (%s); one of %s" % (ctag, why, ", ".join("C" + c for c in list(CTAGS) + deep)))
     if color_range not in (None, "FULL", "LIMITED"):
         raise ValueError("y4m: field XCOLORRANGE=%s: FULL or LIMITED" % color_range)
-    ss = CTAGS[ctag][0]
+    ss = ctag_info(ctag)[0]
     if (ss != 444 and W % 2) or (ss == 420 and H % 2):
         raise ValueError("y4m: fields W%d H%d: odd sizes cannot carry C%s chroma" % (W, H, ctag))
     for k in ("F", "A"):
@@ -215,7 +269,7 @@ class Y4MReader:
         line = self._fh.readline(1024)
         if not line.endswith(b"\n"):
             raise ValueError("y4m: no header line in the first %d bytes" % len(line))
-        self.header = parse_header(line)
+        self.header = parse_header(line, max_depth=16)
         self.frame_bytes = self.header.format().frame_bytes
         pin = torch.cuda.is_available() if pin is None else pin
         self._free, self._full = queue.Queue(), queue.Queue(maxsize=slots)
