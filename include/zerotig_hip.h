@@ -310,6 +310,18 @@ int zt_resample_u8_hwc(const unsigned char* src, unsigned char* dst, int Hi, int
                        const int* bounds, int ksize, zt_stream_t stream);
 int zt_u8hwc_to_planar_f32(const unsigned char* src, float* dst, int H, int W, const float* lut256, zt_stream_t stream);
 
+/* ---- float resize (zt_resample.hip): train.py / predict.py --y4m_size, DESIGN 8g ----------------------------------------------
+ * zt_resample_planar_f32: ONE pass of Pillow's ImagingResample for mode F over planar fp32 along `axis` (1 = rows: src [C][Hi][Wi]
+ *   -> dst [C][Hi][No]; 0 = columns: src [C][Hi][Wi] -> dst [C][No][Wi]):
+ *   ss = 0.0; for t < count: ss = ss + (double)src[first + t] * coef[o][t]; dst = (float)ss -- the multiply and the add are separate
+ *   double operations in tap order.  clamp01 = 1 stores min(max((float)ss, 0), 1) (bicubic overshoots; the model's input is [0, 1]).
+ *   coef: double [No][ksize], bounds: int32 [No][2] = (first source index, tap count <= ksize) -- device arrays, the weights of
+ *   Pillow's precompute_coeffs before any integer normalisation (zero-tig_amd/ingest.py:pil_bicubic_tables_f64).  Nothing is rounded
+ *   to 8 bits between the passes, so it takes the result of zt_yuv16_to_planar_f32 as well.  Rows first, then columns (Resample.c).
+ *   Null pointers, sizes <= 0, axis outside {0, 1}, ksize < 1, src == dst: ZT_EINVAL. */
+int zt_resample_planar_f32(const float* src, float* dst, int C, int Hi, int Wi, int No, int axis, const double* coef, const int* bounds,
+                           int ksize, int clamp01, zt_stream_t stream);
+
 
 /* ---- raw video frames (zt_yuv.hip): 8-bit planar Y'CbCr <-> RGB with chroma resampling, predict.py --y4m_in / --y4m_out -------
  * A frame is the YUV4MPEG2 payload: plane Y [H][W], then U, then V ([H/2][W/2] for ss 420, [H][W/2] for 422, [H][W] for 444),

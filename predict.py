@@ -45,6 +45,10 @@ parser.add_argument("--y4m_out", type=str, default=None,
                     help="write the enhance stream here instead (and no denoise stream); - is standard output, every log line then goes to stderr")
 parser.add_argument("--y4m_resize", type=int, default=0, choices=[0, 1],
                     help="0: enhance at the stream's own size; 1: the loaders' resize((1920, 1080)) first, the output streams are 1920x1080")
+parser.add_argument("--y4m_size", type=str, default=None,
+                    help="WxH: enhance the stream at this size; the decoded frame is resized on the device in float (DESIGN 8g), at "
+                         "every bit depth, and the output streams are W x H.  For weights trained with train.py --y4m_size; cannot be "
+                         "combined with --y4m_resize 1; needs --y4m_in")
 parser.add_argument("--y4m_out_depth", type=int, default=0, choices=[0, 8, 9, 10, 12, 14, 16],
                     help="bits per sample of the output streams; 0: as the input.  An 8-bit stream can leave as 10-bit (the model's fp32 "
                          "result keeps its gradation) and a deep one as 8-bit; needs --y4m_in")
@@ -83,7 +87,8 @@ def main_y4m(args):
     fmt = head.format(args.y4m_matrix)
     if fmt.depth > 8 and args.y4m_resize:
         reader.close()
-        parser.error("--y4m_resize 1 cannot be combined with a %d-bit --y4m_in stream (C%s): the resize is 8-bit" % (fmt.depth, head.ctag))
+        parser.error("--y4m_resize 1 cannot be combined with a %d-bit --y4m_in stream (C%s): the resize is 8-bit; --y4m_size WxH resizes "
+                     "in float at any depth" % (fmt.depth, head.ctag))
     print("Y4M input: %dx%d C%s %d-bit %s %s" % (head.W, head.H, head.ctag, fmt.depth, "full" if head.full else "limited", args.y4m_matrix))
     out_depth = args.y4m_out_depth or fmt.depth
     if out_depth > 8 and fmt.depth == 8 and fmt.ss != 444 and fmt.siting == 0:
@@ -94,7 +99,7 @@ def main_y4m(args):
     for p in model.parameters():
         p.requires_grad = False
     step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080) if args.y4m_resize else None,
-                                                                   yuv=fmt, yuv_out_depth=out_depth)
+                                                                   yuv=fmt, yuv_out_depth=out_depth, yuv_size=args.y4m_size)
     out_head = head.resized(step.yuv_format.W, step.yuv_format.H)._replace(ctag=y4m.ctag_at_depth(head.ctag, out_depth))
     det, cuts, scores, rels = None, [], [], []
     if args.y4m_scene_cut > 0:
@@ -173,6 +178,16 @@ def main():
     args = parser.parse_args()
     if args.y4m_in is None and (args.y4m_out is not None or args.y4m_resize):
         parser.error("--y4m_out / --y4m_resize need --y4m_in")
+    if args.y4m_size is not None:
+        if args.y4m_in is None:
+            parser.error("--y4m_size needs --y4m_in")
+        if args.y4m_resize:
+            parser.error("--y4m_size cannot be combined with --y4m_resize 1: the first is the float resize to WxH, the second the "
+                         "loaders' 8-bit resize to 1920x1080")
+        wh = args.y4m_size.lower().split("x")
+        if len(wh) != 2 or not all(v.isdigit() and int(v) > 0 for v in wh):
+            parser.error("--y4m_size takes WxH, e.g. 1920x1080; got %r" % args.y4m_size)
+        args.y4m_size = (int(wh[0]), int(wh[1]))
     if args.y4m_out_depth and args.y4m_in is None:
         parser.error("--y4m_out_depth needs --y4m_in")
     if args.y4m_scene_cut < 0:

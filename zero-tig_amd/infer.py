@@ -41,20 +41,29 @@ class InferStep:
     construction, so the captured graph has no branch.  A deep input (depth > 8) is never resized: `ingest_size` other than None
     or (W, H) raises ValueError.
 
+    yuv_size=(W, H) (needs yuv= and ingest_size=None): the payload is decoded at the stream's size and resized in float by
+    `Ops.yuv_to_planar_f32_sized` (Pillow's mode-F BICUBIC) inside the step, so also inside the captured graph; it works at
+    every depth, its buffers are allocated once, and `step.yuv_format` is `fmt.resized(W, H)` at the output depth.
+
     Weights are prepared again when a parameter or BatchNorm buffer changed (`_version` / `data_ptr()` of the tensors, e.g. after
     `load_state_dict`); the prepared buffers keep their addresses, so a captured graph stays valid across a reload."""
 
-    def __init__(self, model, use_graph=True, ingest_size=(1920, 1080), png=False, yuv=None, yuv_out_depth=None):
+    def __init__(self, model, use_graph=True, ingest_size=(1920, 1080), png=False, yuv=None, yuv_out_depth=None, yuv_size=None):
         assert int(png) in (0, 1, 2), png
         self.model, self.use_graph, self.ingest_size, self.want_png = model, use_graph, ingest_size, int(png)
         self.graph, self.x, self.out, self.u8, self.png = None, None, None, None, None
         self.fmt, self.yuv, self.yuv_format, self.loaded, self._payload = yuv, None, None, None, None
         assert yuv is not None or yuv_out_depth is None, "yuv_out_depth needs yuv="
+        self.yuv_size, self._sized = None, None
+        if yuv_size is not None:
+            if yuv is None or ingest_size is not None:
+                raise ValueError("InferStep: yuv_size needs yuv= and ingest_size=None (got yuv=%r, ingest_size=%r)" % (yuv, ingest_size))
+            self.yuv_size = (int(yuv_size[0]), int(yuv_size[1]))
         if yuv is not None:
             yuv.check()
-            W, H = (yuv.W, yuv.H) if ingest_size is None else ingest_size
-            if yuv.depth > 8 and (W, H) != (yuv.W, yuv.H):
-                raise ValueError("InferStep: a %d-bit input cannot be resized (%dx%d -> %dx%d): the resize is 8-bit; use ingest_size=None"
+            W, H = self.yuv_size if self.yuv_size is not None else (yuv.W, yuv.H) if ingest_size is None else ingest_size
+            if yuv.depth > 8 and (W, H) != (yuv.W, yuv.H) and self.yuv_size is None:
+                raise ValueError("InferStep: a %d-bit input cannot be resized (%dx%d -> %dx%d): the resize is 8-bit; use ingest_size=None, and yuv_size=(W, H) for the float resize"
                                  % (yuv.depth, yuv.W, yuv.H, W, H))
             # the output streams: same layout at the output size, at the input's depth unless another is asked for
             self.yuv_format = yuv.resized(W, H)._replace(depth=yuv.depth if yuv_out_depth is None else int(yuv_out_depth)).check()
@@ -108,6 +117,10 @@ class InferStep:
         """the payload in `self._payload` -> the model's input (x: the static input buffer, or None)"""
         if self.yuv_format[:2] == self.fmt[:2]:
             return ops.yuv_to_planar_f32(payload, self.fmt, out=x)
+        if self.yuv_size is not None:
+            if self._sized is None or self._sized["decode"].device != payload.device:
+                self._sized = ops.sized_bufs(self.fmt, self.yuv_size, payload.device)
+            return ops.yuv_to_planar_f32_sized(payload, self.fmt, self.yuv_size, out=x, bufs=self._sized)
         return ops.ingest_u8(ops.yuv_to_rgb_u8(payload, self.fmt), out=x, size=self.ingest_size)
 
     def _body(self, eng, rp, x, payload=None):

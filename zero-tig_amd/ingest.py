@@ -49,6 +49,32 @@ def pil_bicubic_tables(in_size, out_size):
     return coef, bounds, ksize
 
 
+def pil_bicubic_tables_f64(in_size, out_size):
+    """-> (coef float64 [out_size, ksize], bounds int32 [out_size, 2] = (first source index, tap count), ksize): the weights of
+    `pil_bicubic_tables` before their integer normalisation, w[x] / ww in double precision -- what Pillow's mode-F resampler
+    multiplies with (csrc/zt_resample.hip)."""
+    scale = filterscale = float(in_size) / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = 2.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    coef = np.zeros((out_size, ksize), np.float64)
+    bounds = np.zeros((out_size, 2), np.int32)
+    ss = 1.0 / filterscale
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for x in range(xmax):
+            coef[xx, x] = w[x] / ww if ww != 0.0 else w[x]
+        bounds[xx] = (xmin, xmax)
+    return coef, bounds, ksize
+
+
 def to_tensor_lut():
     """ToTensor's `byte / 255` as a table: float32(k) / float32(255), correctly rounded by the host's IEEE division (what torch's
     CPU `div` computes), so the device result is bit-identical."""

@@ -314,6 +314,75 @@ class Ops:
                       self._to_tensor_lut(dev), self._s(payload))
         return out
 
+    # ---- float resize (zt_resample.hip) -----------------------------------------------------------------
+    def _f64_tables(self, n_in, n_out, dev):
+        """the double-precision tables of `ingest.pil_bicubic_tables_f64` on `dev`, uploaded once per (in, out)"""
+        from . import ingest
+        cache = self.__dict__.setdefault("_resample_tables", {})
+        key = (int(n_in), int(n_out), str(dev))
+        if key not in cache:
+            coef, bounds, ks = ingest.pil_bicubic_tables_f64(int(n_in), int(n_out))
+            cache[key] = (torch.from_numpy(coef).to(dev), torch.from_numpy(bounds).to(dev), ks)
+        return cache[key]
+
+    def resize_planar_f32(self, x, size, clamp=True, out=None, tmp=None):
+        """fp32 [1,C,H,W] -> fp32 [1,C,H',W'], size = (W', H') like PIL: Pillow's BICUBIC resize of a mode-F image per plane
+        (double accumulation in tap order, rounded to float after each pass), horizontal pass first, then vertical; a pass whose
+        size is unchanged is skipped, as Pillow does.  clamp: the last pass that runs stores min(max(v, 0), 1).  With both sizes
+        unchanged the result is a copy into `out`, or `x` itself when `out` is None.  `tmp`: the [1,C,H,W'] intermediate of a
+        two-pass resize (a caller that is captured into a graph keeps it)."""
+        _f32c(x)
+        assert x.dim() == 4 and x.shape[0] == 1, tuple(x.shape)
+        _, C, H0, W0 = (int(v) for v in x.shape)
+        W, H = (int(v) for v in size)
+        assert W > 0 and H > 0, size
+        dev, s = x.device, self._s(x)
+        if out is not None:
+            assert tuple(out.shape) == (1, C, H, W) and out.dtype == torch.float32 and out.is_contiguous() and out.device == dev, \
+                (tuple(out.shape), (1, C, H, W))
+        if (W, H) == (W0, H0):
+            if out is None:
+                return x
+            out.copy_(x)
+            return out
+        if out is None:
+            out = torch.empty((1, C, H, W), dtype=torch.float32, device=dev)
+        assert out.data_ptr() != x.data_ptr()
+        cur = x
+        if W0 != W:
+            coef, bounds, ks = self._f64_tables(W0, W, dev)
+            last = H0 == H
+            if last:
+                nxt = out
+            else:
+                nxt = torch.empty((1, C, H0, W), dtype=torch.float32, device=dev) if tmp is None else tmp
+                assert tuple(nxt.shape) == (1, C, H0, W) and nxt.dtype == torch.float32 and nxt.is_contiguous() and nxt.device == dev
+            self.lib.call("zt_resample_planar_f32", cur, nxt, C, H0, W0, W, 1, coef, bounds, ks, int(bool(clamp) and last), s)
+            cur = nxt
+        if H0 != H:
+            coef, bounds, ks = self._f64_tables(H0, H, dev)
+            self.lib.call("zt_resample_planar_f32", cur, out, C, H0, W, H, 0, coef, bounds, ks, int(bool(clamp)), s)
+        return out
+
+    def sized_bufs(self, fmt, size, dev):
+        """the buffers `yuv_to_planar_f32_sized` works in: {"decode": [1,3,H,W], "tmp": [1,3,H,W'] or None}"""
+        W, H = (int(v) for v in size)
+        two = W != fmt.W and H != fmt.H
+        return {"decode": torch.empty((1, 3, fmt.H, fmt.W), dtype=torch.float32, device=dev),
+                "tmp": torch.empty((1, 3, fmt.H, W), dtype=torch.float32, device=dev) if two else None}
+
+    def yuv_to_planar_f32_sized(self, payload, fmt, size, out=None, bufs=None):
+        """Y4M payload of `fmt` (8-bit or deep) -> fp32 [1,3,H',W'] in [0,1], size = (W', H'): `yuv_to_planar_f32` at the source
+        size followed by `resize_planar_f32` (clamped), bit for bit.  `bufs` (of `sized_bufs`) holds the decode buffer and the
+        intermediate, so a caller that is captured into a graph keeps stable addresses.  The result never aliases `bufs`."""
+        W, H = (int(v) for v in size)
+        if bufs is None:
+            bufs = self.sized_bufs(fmt, size, payload.device)
+        x = self.yuv_to_planar_f32(payload, fmt, out=bufs["decode"])
+        if out is None:
+            out = torch.empty((1, 3, H, W), dtype=torch.float32, device=payload.device)
+        return self.resize_planar_f32(x, (W, H), clamp=True, out=out, tmp=bufs["tmp"])
+
     def rgb_f32_to_yuv(self, x, fmt, out=None):
         """[1,3,H,W] fp32 in [0,1] -> Y4M payload (1-D uint8) of `fmt`: the levels `quantize_u8(x, 0)` makes (predict.py's
         truncation), converted and chroma-subsampled in the same pass.  A deep format (depth > 8): from the 16-bit levels

@@ -120,12 +120,24 @@ class TrainStep:
     becomes one graph launch.  The frame is copied into a static input buffer (host -> HBM or HBM -> HBM) and the recurrent
     cache `last_H3 / last_s3` lives in static buffers, so the captured addresses stay valid from frame to frame.  New-sequence
     frames (rare: once per clip) and the gradient all-reduce + clip + Adam launch (which takes the host-side step count) stay
-    eager.  The model must not be moved, and `last_H3 / last_s3` must not be re-assigned by the caller, after the capture."""
+    eager.  The model must not be moved, and `last_H3 / last_s3` must not be re-assigned by the caller, after the capture.
 
-    def __init__(self, model, optimizer, use_graph=True, ingest_size=(1920, 1080)):
+    yuv=fmt (a `y4m.YuvFormat`): `frame` is the 1-D uint8 payload of a raw video frame, pinned or on the device.  `_load` copies it
+    into a static device buffer (`step.loaded` is the event behind that copy: a reader may reuse its ring slot once it has
+    completed) and decodes it into the input with `Ops.yuv_to_planar_f32`, or, with yuv_size=(W, H), `Ops.yuv_to_planar_f32_sized`
+    (the float resize of DESIGN 8g, any depth).  As for every other frame type the load runs before the replay and is not captured;
+    the input shape is (1, 3, H', W').  `ingest_size` plays no part then."""
+
+    def __init__(self, model, optimizer, use_graph=True, ingest_size=(1920, 1080), yuv=None, yuv_size=None):
         """ingest_size: (W, H) that decoded uint8 frames are resized to (the reference loader's fixed 1920 x 1080); None = keep."""
         self.model, self.opt, self.use_graph, self.ingest_size = model, optimizer, use_graph, ingest_size
         self.graph, self.x, self.loss, self.n_eager_steady, self._mode = None, None, None, 0, None
+        self.fmt, self.yuv_size, self.loaded, self._payload, self._sized = yuv, None, None, None, None
+        if yuv_size is not None and yuv is None:
+            raise ValueError("TrainStep: yuv_size needs yuv=")
+        if yuv is not None:
+            yuv.check()
+            self.yuv_size = (yuv.W, yuv.H) if yuv_size is None else (int(yuv_size[0]), int(yuv_size[1]))
 
     def _body(self, x):
         """zero_grad + loss + gradients straight into the optimizer's flat bucket (no autograd bookkeeping, no ATen math)"""
@@ -139,6 +151,8 @@ class TrainStep:
         only) go through the ingest kernels: PIL-exact resize to 1920x1080 + ToTensor (multi_read_data.py:127-132), written
         straight into `out` when given."""
         import torch
+        if self.fmt is not None:
+            return self._load_yuv(frame, dev, out)
         if frame.dtype == torch.uint8:
             self.model._plan()
             return self.model._ops.ingest_u8(frame.to(dev, non_blocking=True), out=out, size=self.ingest_size)
@@ -146,6 +160,26 @@ class TrainStep:
             return frame.to(dev, non_blocking=True)
         out.copy_(frame, non_blocking=True)
         return out
+
+    def _load_yuv(self, frame, dev, out=None):
+        """payload -> static device buffer (event `self.loaded`) -> decoded, and resized when asked for, into `out`"""
+        import torch
+        fmt = self.fmt
+        assert frame.dtype == torch.uint8 and frame.dim() == 1 and frame.numel() == fmt.frame_bytes, \
+            (frame.dtype, tuple(frame.shape), fmt.frame_bytes)
+        if self._payload is None or self._payload.device != dev:
+            self._payload = torch.empty(fmt.frame_bytes, dtype=torch.uint8, device=dev)
+            self._sized = None
+        self._payload.copy_(frame, non_blocking=True)
+        self.loaded = torch.cuda.Event()
+        self.loaded.record()
+        self.model._plan()
+        ops = self.model._ops
+        if self.yuv_size == (fmt.W, fmt.H):
+            return ops.yuv_to_planar_f32(self._payload, fmt, out=out)
+        if self._sized is None:
+            self._sized = ops.sized_bufs(fmt, self.yuv_size, dev)
+        return ops.yuv_to_planar_f32_sized(self._payload, fmt, self.yuv_size, out=out, bufs=self._sized)
 
     def __call__(self, frame, is_new_seq=False):
         import torch
@@ -157,7 +191,9 @@ class TrainStep:
                 loss = self._body(self._load(frame, dev))
             self.opt.step()
             return loss
-        if frame.dtype == torch.uint8:
+        if self.fmt is not None:
+            shape = (1, 3, self.yuv_size[1], self.yuv_size[0])
+        elif frame.dtype == torch.uint8:
             Wi, Hi = self.ingest_size if self.ingest_size is not None else (frame.shape[-2], frame.shape[-3])
             shape = (1, 3, Hi, Wi)
         else:

@@ -254,6 +254,50 @@ def _open_in(path):
     return (sys.stdin.buffer, False) if path == "-" else (open(path, "rb"), True)
 
 
+def _seekable(fh):
+    try:
+        return bool(fh.seekable())
+    except (AttributeError, ValueError):
+        return False
+
+
+def count_frames(path):
+    """the number of frames of a Y4M file: the header is parsed, then per frame the FRAME line is read and the payload stepped over
+    with a seek (no payload is read, nothing touches the GPU).  A last frame with fewer bytes than the header promises raises the
+    reader's ValueError; a pipe cannot be counted."""
+    with open(path, "rb") as fh:
+        if not _seekable(fh):
+            raise ValueError("y4m: %s is not seekable: its frames cannot be counted" % path)
+        line = fh.readline(1024)
+        if not line.endswith(b"\n"):
+            raise ValueError("y4m: no header line in the first %d bytes" % len(line))
+        frame_bytes = parse_header(line, max_depth=16).format().frame_bytes
+        size = fh.seek(0, 2)
+        fh.seek(len(line))
+        n = 0
+        while True:
+            line = fh.readline(1024)
+            if not line:
+                return n
+            if not (line.startswith(b"FRAME") and line.endswith(b"\n")):
+                raise ValueError("y4m: frame %d: expected a FRAME line, got %r" % (n, line[:32]))
+            pos = fh.tell()
+            if pos + frame_bytes > size:
+                raise ValueError("y4m: truncated stream: frame %d has %d of %d bytes" % (n, size - pos, frame_bytes))
+            fh.seek(frame_bytes, 1)
+            n += 1
+
+
+def rank_share(n, rank, world):
+    """frames of an n-frame stream that `rank` of `world` trains on -> (first, count, steps_per_epoch): contiguous shares of
+    per = ceil(n / world) frames, as train.py cuts the frame list of a dataset (the last shares may be short or empty);
+    every rank takes `steps_per_epoch` = the smallest share, so that all of them make the same number of all-reduces."""
+    assert n >= 0 and world >= 1 and 0 <= rank < world, (n, rank, world)
+    per = (n + world - 1) // world
+    shares = [max(min(n, (r + 1) * per) - r * per, 0) for r in range(world)]
+    return rank * per, shares[rank], min(shares)
+
+
 class Y4MReader:
     """reader = Y4MReader(path or "-"); reader.header; for payload in reader: ...
 
@@ -261,10 +305,15 @@ class Y4MReader:
     overrides).  It is valid until the next `next()`; `release(event)` hands it back earlier and makes the reader thread wait for
     `event` (the asynchronous copy to the device) before it overwrites the buffer -- a loop that copies with non_blocking=True
     must release with that event.  A stream that ends inside a frame raises ValueError; a clean end of file ends the iteration.
-    `wait` accumulates the seconds `next()` spent blocked."""
+    `wait` accumulates the seconds `next()` spent blocked.
 
-    def __init__(self, path, slots=4, pin=None, fh=None):
-        assert slots >= 2
+    `first` / `count`: the iteration covers frames first .. first + count - 1 of the stream (count None = to the end; a share of
+    `train.py`'s ranks).  On a seekable file the frames before `first` are stepped over (the FRAME line is read, the payload
+    skipped with a seek); on a pipe they are read and dropped.  A `first` past the end gives an empty iteration."""
+
+    def __init__(self, path, slots=4, pin=None, fh=None, first=0, count=None):
+        assert slots >= 2 and first >= 0 and (count is None or count >= 0), (slots, first, count)
+        self._first, self._count = int(first), None if count is None else int(count)
         self._fh, self._own = (fh, False) if fh is not None else _open_in(path)
         line = self._fh.readline(1024)
         if not line.endswith(b"\n"):
@@ -279,10 +328,31 @@ class Y4MReader:
         self._thread = threading.Thread(target=self._run, name="y4m-reader", daemon=True)
         self._thread.start()
 
+    def _skip(self):
+        """step over the frames before `first` -> False when the stream ends there"""
+        seekable = _seekable(self._fh)
+        for n in range(self._first):
+            line = self._fh.readline(1024)
+            if not line:
+                return False
+            if not (line.startswith(b"FRAME") and line.endswith(b"\n")):
+                raise ValueError("y4m: frame %d: expected a FRAME line, got %r" % (n, line[:32]))
+            if seekable:
+                self._fh.seek(self.frame_bytes, 1)
+            else:
+                left = self.frame_bytes
+                while left:
+                    k = len(self._fh.read(min(left, 1 << 20)))
+                    if not k:
+                        raise ValueError("y4m: truncated stream: frame %d has %d of %d bytes" % (n, self.frame_bytes - left, self.frame_bytes))
+                    left -= k
+        return True
+
     def _run(self):
-        n = 0
+        n = self._first
         try:
-            while True:
+            more = self._skip()
+            while more and (self._count is None or n < self._first + self._count):
                 item = self._free.get()
                 if item is None:
                     return
