@@ -346,7 +346,7 @@ int zt_yuv_to_planar_f32(const unsigned char* src, float* dst, int H, int W, int
                          zt_stream_t stream);
 int zt_rgb_f32_to_yuv(const float* src, unsigned char* dst, int H, int W, int ss, int siting, const int* coef, zt_stream_t stream);
 
-/* ---- high-bit-depth raw video frames (zt_yuv16.hip): planar Y'CbCr of depth B in {9, 10, 12, 14, 16} <-> RGB, DESIGN 8f ----------
+/* ---- high-bit-depth raw video frames (zt_yuv.hip, the grid in zt_scene.hip): planar Y'CbCr of depth B in {9 .. 16} <-> RGB, DESIGN 8f
  * The payload has the plane shapes above as little-endian uint16, the value in the low B bits; a sample above m = 2^B - 1 is read
  * as m.  ss, siting, the tap tables and the footprints are those of the 8-bit entry points.  coef: HOST pointer to 64-bit integers,
  * round(c * 2^20) with matrix, range and depth folded in (zero-tig_amd/y4m.py); every entry must fit 32 bits.  mid = 2^(B-1).

@@ -1,5 +1,6 @@
 """Scene cuts in a Y4M stream: the two integer kernels of zt_scene.hip against the definition restated here in numpy
 int64, the host rule, `SceneCut` on synthetic clips with one cut, `InferStep` across a cut and predict.py --y4m_scene_cut.
+The grid kernel is a template over the sample type; its 2-byte instantiation (deep planes) is pinned in test_y4m_deep.py.
 
 The definition.  The luma plane Y [H][W] (the first H * W bytes of a payload) is cut into 16 x 16 cells, gh = ceil(H / 16) rows of
 gw = ceil(W / 16); edge cells hold the pixels that exist.  G[i][j] = sum over the cell of max(Y - yo, 0) (uint32; yo = 16 for

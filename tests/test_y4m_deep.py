@@ -1,4 +1,4 @@
-"""High-bit-depth raw video: the kernels of zt_yuv16.hip against the integer definition restated here in numpy int64
+"""High-bit-depth raw video: the deep kernels of zt_yuv.hip against the integer definition restated here in numpy int64
 and against the float64 statement of BT.601 / BT.709 (test_y4m.py's bilinear chroma, no 2^20 anywhere), the scene-cut grid of a
 deep plane, the Y4M container with 16-bit samples, InferStep(yuv=, yuv_out_depth=) and predict.py --y4m_out_depth.  What is
 pinned is this definition; agreement with libswscale's rounding is not.  The chroma taps (`_up16`, `_upf`, `_foot`) and the flat

@@ -21,7 +21,7 @@
     --precision bf16 --y4m_in over it (two Y4M streams written), measured like the PNG settings, and "convert" holds the three
     conversions alone at 1080p: HIP-event median over --reps calls, the bytes each moves and the share of the HBM peak.
     --y4m-depth B (9 .. 16): the same loop over the clip as C420pB as "y4m_pB", its runs alternating with those of "y4m", and the
-    two deep conversions (zt_yuv16.hip) next to the 8-bit ones in "convert".
+    two deep conversions (zt_yuv.hip) next to the 8-bit ones in "convert".
     --scene-cut T [T ..]: the same loop with predict.py --y4m_scene_cut T as "y4m_scene_cut_T", its runs alternating with those of
     "y4m" (flag off), with the time the loop was blocked for the detector (scene_wait_ms) and the sequences restarted (cuts); "scene"
     holds the two kernels of zt_scene.hip alone.

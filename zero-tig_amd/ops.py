@@ -280,7 +280,7 @@ class Ops:
         self.lib.call("zt_u8hwc_to_planar_f32", cur, out, H, W, self._to_tensor_lut(dev), s)
         return out
 
-    # ---- raw video frames (zt_yuv.hip) --------------------------------------------------------------------------
+    # ---- raw video frames (zt_yuv.hip, 8-bit and deep) -----------------------------------------------------------
     def _yuv_payload(self, payload, fmt):
         fmt.check()
         assert payload.dtype == torch.uint8 and payload.dim() == 1 and payload.is_contiguous() and payload.numel() == fmt.frame_bytes, \

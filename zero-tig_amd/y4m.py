@@ -8,7 +8,7 @@ tags C420p10 ... C444p16).  Video tools read and write it through pip
 
 `parse_header` -> `Header`; `Header.format(matrix)` -> `YuvFormat`, which fixes the conversion (subsampling, chroma siting, matrix,
 range, depth) and carries the coefficient tables: round(c * 2^14) of the values derived from (Kr, Kb) in double precision (DESIGN 8d);
-round(c * 2^20), int64, for the 16-bit levels of a deep format (csrc/zt_yuv16.hip).
+round(c * 2^20), int64, for the 16-bit levels of a deep format (the same kernels at their deep scale).
 `Y4MReader` is an iterator over payloads: one thread reads the stream into a bounded ring of (pinned) buffers, so the loop's
 `next()` is a queue pop.  `Y4MWriter` follows `pngwriter.PngWriter`: a ring of pinned buffers, an asynchronous copy on the step's
 stream plus an event per frame, a bounded queue, ONE thread per stream (frames land in order), `close()` drains and re-raises.
@@ -45,10 +45,6 @@ def ctag_at_depth(ctag, depth):
     if depth == d:
         return ctag
     return "%dp%d" % (ss, depth) if depth > 8 else {420: "420mpeg2", 422: "422", 444: "444"}[ss]
-
-
-def _q(v):
-    return int(round(v * (1 << S)))
 
 
 class YuvFormat(collections.namedtuple("YuvFormat", "W H ss siting matrix full depth", defaults=(8,))):
@@ -93,50 +89,37 @@ class YuvFormat(collections.namedtuple("YuvFormat", "W H ss siting matrix full d
     def decode_coef(self):
         """int32 [6] on the host: yo, CY, CRV, CGU, CGV, CBU (zt_yuv_to_rgb_u8 / zt_yuv_to_planar_f32); for depth > 8 the int64
         table of zt_yuv16_to_planar_f32"""
-        return (_coef16(self.matrix, self.full, self.depth) if self.depth > 8 else _coef(self.matrix, self.full))[0]
+        return _coef(self.matrix, self.full, self.depth)[0]
 
     def encode_coef(self):
         """int32 [10] on the host: yo, CYR, CYG, CYB, CUR, CUG, CUB, CVR, CVG, CVB (zt_rgb_f32_to_yuv); for depth > 8 the int64
         table of zt_rgb_f32_to_yuv16"""
-        return (_coef16(self.matrix, self.full, self.depth) if self.depth > 8 else _coef(self.matrix, self.full))[1]
+        return _coef(self.matrix, self.full, self.depth)[1]
 
 
 _COEF = {}
 
 
-def _coef(matrix, full):
-    key = (matrix, int(bool(full)))
-    if key not in _COEF:
-        kr, kb = KR_KB[matrix]
-        kg = 1.0 - kr - kb
-        cy, cs, yo = (1.0, 1.0, 0) if full else (255.0 / 219.0, 255.0 / 224.0, 16)
-        dec = [yo, _q(cy), _q(cs * 2 * (1 - kr)), _q(cs * 2 * kb * (1 - kb) / kg), _q(cs * 2 * kr * (1 - kr) / kg), _q(cs * 2 * (1 - kb))]
-        cyr, cyb = _q(kr / cy), _q(kb / cy)
-        cur, cub = _q(-kr / (2 * (1 - kb)) / cs), _q(0.5 / cs)
-        cvr, cvb = _q(0.5 / cs), _q(-kb / (2 * (1 - kr)) / cs)
-        enc = [yo, cyr, _q(1.0 / cy) - cyr - cyb, cyb, cur, -(cur + cub), cub, cvr, -(cvr + cvb), cvb]
-        _COEF[key] = (torch.tensor(dec, dtype=torch.int32), torch.tensor(enc, dtype=torch.int32))
-    return _COEF[key]
-
-
-def _coef16(matrix, full, depth):
-    """the tables of DESIGN 8f: 16-bit RGB levels against samples of `depth` bits, round(c * 2^20), int64"""
+def _coef(matrix, full, depth):
+    """(decode, encode) tables: RGB levels 0..255 against 8-bit samples, round(c * 2^14), int32; 0..65535 against samples
+    of `depth` > 8 bits, round(c * 2^20), int64"""
     key = (matrix, int(bool(full)), int(depth))
     if key not in _COEF:
         kr, kb = KR_KB[matrix]
         kg = 1.0 - kr - kb
+        levels, s, dtype = (255.0, S, torch.int32) if depth == 8 else (65535.0, S16, torch.int64)
         k = 1 << (depth - 8)
         yo, yr, cr = (0, (1 << depth) - 1, (1 << depth) - 1) if full else (16 * k, 219 * k, 224 * k)
 
         def q(v):
-            return int(round(v * (1 << S16)))
-        cy, cs = 65535.0 / yr, 65535.0 / cr
+            return int(round(v * (1 << s)))
+        cy, cs = levels / yr, levels / cr
         dec = [yo, q(cy), q(cs * 2 * (1 - kr)), q(cs * 2 * kb * (1 - kb) / kg), q(cs * 2 * kr * (1 - kr) / kg), q(cs * 2 * (1 - kb))]
-        cyr, cyb = q(kr * yr / 65535.0), q(kb * yr / 65535.0)
-        cur, cub = q(-kr / (2 * (1 - kb)) * cr / 65535.0), q(0.5 * cr / 65535.0)
-        cvr, cvb = q(0.5 * cr / 65535.0), q(-kb / (2 * (1 - kr)) * cr / 65535.0)
-        enc = [yo, cyr, q(yr / 65535.0) - cyr - cyb, cyb, cur, -(cur + cub), cub, cvr, -(cvr + cvb), cvb]
-        _COEF[key] = (torch.tensor(dec, dtype=torch.int64), torch.tensor(enc, dtype=torch.int64))
+        cyr, cyb = q(kr * yr / levels), q(kb * yr / levels)
+        cur, cub = q(-kr / (2 * (1 - kb)) * cr / levels), q(0.5 * cr / levels)
+        cvr, cvb = q(0.5 * cr / levels), q(-kb / (2 * (1 - kr)) * cr / levels)
+        enc = [yo, cyr, q(yr / levels) - cyr - cyb, cyb, cur, -(cur + cub), cub, cvr, -(cvr + cvb), cvb]
+        _COEF[key] = (torch.tensor(dec, dtype=dtype), torch.tensor(enc, dtype=dtype))
     return _COEF[key]
 
 
