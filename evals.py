@@ -8,8 +8,10 @@ Ground truth: `<...>/input/<scene>/low_light_*/N.png` -> `<...>/gt/<scene>/norma
 import argparse
 import json
 import logging
+import math
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -29,7 +31,7 @@ parser.add_argument("--seed", type=int, default=2)
 parser.add_argument("--of_scale", type=int, default=3)
 parser.add_argument("--dataset", type=str, default="RLV")
 parser.add_argument("--gain", type=int, default=100, help="kept for CLI compatibility (unused upstream as well)")
-parser.add_argument("--save_images", type=int, default=20, help="write the first N result pairs (evals.py:162)")
+parser.add_argument("--save_images", type=int, default=None, help="write the first N result pairs (evals.py:162); default 20")
 parser.add_argument("--hist_match", type=int, default=1, help="0: skip histogram matching and the *_HM metrics (evals.py:114)")
 parser.add_argument("--lpips_weights", type=str, default=None,
                     help="torch.save(lpips.LPIPS(net='vgg').state_dict(), FILE); default: no LPIPS (fields null)")
@@ -41,10 +43,355 @@ parser.add_argument("--graph", type=int, default=0, choices=[0, 1],
 parser.add_argument("--device_png", type=int, default=0, choices=[0, 1, 2],
                     help="1: the --save_images files are deflated on the device and written by a threaded writer (same pixels); "
                          "2: the same with run-length matches, for frames with flat areas (never larger than 1)")
+parser.add_argument("--y4m_in", type=str, default=None,
+                    help="raw video in: the low-light YUV4MPEG2 file, or - for standard input (the layouts of predict.py --y4m_in, 8 to 16 "
+                         "bits); with --y4m_gt it replaces the dataset walk: the stream is enhanced as by predict.py --y4m_in and every "
+                         "frame is graded against the frame of --y4m_gt; needs --graph 1")
+parser.add_argument("--y4m_gt", type=str, default=None,
+                    help="the ground-truth YUV4MPEG2 file (a file, not -): as many frames as --y4m_in, the same size after --y4m_size; "
+                         "with the layout of the denoise stream (size, subsampling, depth) the plane metrics are reported as well")
+parser.add_argument("--y4m_out", type=str, default=None, help="also write the enhance stream to this file while evaluating")
+parser.add_argument("--y4m_size", type=str, default=None,
+                    help="WxH: both streams are decoded at their own size and resized on the device in float (DESIGN 8g) before the model "
+                         "and the RGB metrics; needs --y4m_in")
+parser.add_argument("--y4m_out_depth", type=int, default=0, choices=[0, 8, 9, 10, 12, 14, 16],
+                    help="bits per sample of the enhance / denoise payloads; 0: as the input; needs --y4m_in")
+parser.add_argument("--y4m_matrix", type=str, default="bt709", choices=["bt709", "bt601"],
+                    help="the Y'CbCr matrix of both streams (Y4M cannot carry it)")
+parser.add_argument("--y4m_scene_cut", type=float, default=0.0,
+                    help="0: one stream is one sequence; T > 0: a frame of --y4m_in whose scene score (DESIGN 8e) exceeds T starts a new "
+                         "sequence, as in predict.py")
+parser.add_argument("--y4m_cuts_json", type=str, default=None,
+                    help="write {threshold, cuts: [frame indices], score: [...], rel: [...]} here at the end; needs --y4m_scene_cut and --y4m_in")
+parser.add_argument("--timing_json", type=str, default=None,
+                    help="with --y4m_in: write the loop's host-side time split per frame (decode wait, step, metric launches, table "
+                         "read-backs, writer) and its frames per second to this file")
+parser.add_argument("--y4m_frames_json", type=str, default=None,
+                    help="write one record per frame here (plane SSEs and SSIMs, the RGB metrics, the cut flag); needs --y4m_in")
+
+CHUNK = 64                                         # frames per read-back of the metric table
+# columns of the metric table's two halves: int64 (exact sums) and float64
+I_SSE, I_SQ, I_SQ_HM, I_COLS = 0, 3, 4, 5
+F_SSIM, F_SSIM_HM, F_SSIM_P, F_LP, F_LP_HM, F_COLS = 0, 1, 2, 5, 10, 15
+
+
+def check_y4m_args(args):
+    """every argument check of the video mode, before anything touches the device -> True when the video mode was asked for"""
+    if args.y4m_in is None:
+        for flag in ("y4m_gt", "y4m_out", "y4m_size", "y4m_cuts_json", "y4m_frames_json", "timing_json"):
+            if getattr(args, flag) is not None:
+                parser.error("--%s needs --y4m_in" % flag)
+        if args.y4m_out_depth:
+            parser.error("--y4m_out_depth needs --y4m_in")
+        if args.y4m_scene_cut != 0:
+            parser.error("--y4m_scene_cut needs --y4m_in")
+        return False
+    if args.y4m_gt is None:
+        parser.error("--y4m_in needs --y4m_gt: the ground-truth stream the frames are graded against")
+    if args.y4m_gt == "-":
+        parser.error("--y4m_gt must be a file: only --y4m_in can be read from standard input")
+    if not args.graph:
+        parser.error("--y4m_in needs --graph 1 (the colour conversion runs inside InferStep); --graph is %d" % args.graph)
+    if args.device_png:
+        parser.error("--y4m_in writes Y4M streams, not PNG files: --device_png %d cannot be combined with it" % args.device_png)
+    if args.save_images is not None:
+        parser.error("--y4m_in writes no image files: --save_images cannot be combined with it (--y4m_out FILE keeps the enhance stream)")
+    if args.y4m_out == "-":
+        parser.error("--y4m_out must be a file: standard output carries the log")
+    if args.y4m_size is not None:
+        wh = args.y4m_size.lower().split("x")
+        if len(wh) != 2 or not all(v.isdigit() and int(v) > 0 for v in wh):
+            parser.error("--y4m_size takes WxH, e.g. 1920x1080; got %r" % args.y4m_size)
+        args.y4m_size = (int(wh[0]), int(wh[1]))
+    if args.y4m_scene_cut < 0:
+        parser.error("--y4m_scene_cut is a threshold in [0, 1], 0 = off; got %g" % args.y4m_scene_cut)
+    if args.y4m_cuts_json is not None and not args.y4m_scene_cut > 0:
+        parser.error("--y4m_cuts_json needs --y4m_scene_cut T (T > 0) and --y4m_in")
+    if not os.path.isfile(args.y4m_gt):
+        parser.error("--y4m_gt %s: no such file" % args.y4m_gt)
+    return True
+
+
+class GroundTruth:
+    """The ground-truth stream on the device: `load(payload)` copies a frame's payload into a static buffer (`loaded` is the event
+    behind that copy) and decodes it the way InferStep decodes its input -- `Ops.yuv_to_planar_f32`, or
+    `Ops.yuv_to_planar_f32_sized` when the streams are resized -- into `rgb` [1,3,H,W]; `payload` is the device copy."""
+
+    def __init__(self, ops, fmt, size, dev):
+        self.ops, self.fmt = ops, fmt
+        self.size = None if size is None or tuple(size) == (fmt.W, fmt.H) else (int(size[0]), int(size[1]))
+        W, H = self.size or (fmt.W, fmt.H)
+        self.payload = torch.empty(fmt.frame_bytes, dtype=torch.uint8, device=dev)
+        self.rgb = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
+        self._bufs = ops.sized_bufs(fmt, self.size, dev) if self.size else None
+        self.loaded = None
+
+    def load(self, payload):
+        self.payload.copy_(payload, non_blocking=True)
+        self.loaded = torch.cuda.Event()
+        self.loaded.record()
+        if self.size is None:
+            return self.ops.yuv_to_planar_f32(self.payload, self.fmt, out=self.rgb)
+        return self.ops.yuv_to_planar_f32_sized(self.payload, self.fmt, self.size, out=self.rgb, bufs=self._bufs)
+
+
+def _psnr_of(sq, n):
+    return float("inf") if sq == 0 else 10.0 * math.log10(255.0 ** 2 * n / sq)
+
+
+def main_y4m(args):
+    """--y4m_in LOW --y4m_gt GT: the low stream through InferStep(yuv=) as in predict.py, every frame graded against the ground
+    truth's.  Each metric kernel writes into a row of a table on the device; the table is read back every CHUNK frames (and at the
+    end), one chunk late, so the host keeps running ahead of the device."""
+    import importlib
+    y4m = importlib.import_module("zero-tig_amd.y4m")
+    os.makedirs(args.save, exist_ok=True)
+    logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(asctime)s %(message)s", datefmt="%m/%d %I:%M:%S %p")
+    logging.getLogger().addHandler(logging.FileHandler(os.path.join(args.save, "log.txt")))
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    dev = torch.device("cuda", args.gpu)
+    reader = y4m.Y4MReader(args.y4m_in)
+    try:
+        gt_reader = y4m.Y4MReader(args.y4m_gt)
+    except BaseException:
+        reader.close()
+        raise
+    writer = None
+    try:
+        head, gt_head = reader.header, gt_reader.header
+        fmt, gt_fmt = head.format(args.y4m_matrix), gt_head.format(args.y4m_matrix)
+        for name, h, f in (("input", head, fmt), ("ground truth", gt_head, gt_fmt)):
+            logging.info("Y4M %s: %dx%d C%s %d-bit %s %s", name, h.W, h.H, h.ctag, f.depth, "full" if h.full else "limited", args.y4m_matrix)
+        out_depth = args.y4m_out_depth or fmt.depth
+        W, H = args.y4m_size or (fmt.W, fmt.H)
+        if args.y4m_size is None and (gt_fmt.W, gt_fmt.H) != (W, H):
+            raise ValueError("the streams differ in frame size: --y4m_in is %dx%d, --y4m_gt is %dx%d (--y4m_size WxH resizes both)"
+                             % (fmt.W, fmt.H, gt_fmt.W, gt_fmt.H))
+        model = Finetunemodel(args).to(dev)
+        model.eval()
+        for p in model.parameters():
+            p.requires_grad = False
+        step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=None, yuv=fmt,
+                                                                       yuv_out_depth=out_depth, yuv_size=args.y4m_size)
+        ops = utils._ops()
+        out_fmt = step.yuv_format
+        gt = GroundTruth(ops, gt_fmt, (W, H), dev)
+        planes_on, why = True, None
+        if (gt_fmt.W, gt_fmt.H, gt_fmt.ss, gt_fmt.depth) != (out_fmt.W, out_fmt.H, out_fmt.ss, out_fmt.depth):
+            planes_on = False
+            why = "the denoise payload is %dx%d %d %d-bit, the ground truth %dx%d %d %d-bit" % (
+                out_fmt.W, out_fmt.H, out_fmt.ss, out_fmt.depth, gt_fmt.W, gt_fmt.H, gt_fmt.ss, gt_fmt.depth)
+        elif min(out_fmt.chroma_shape) < 7 or min(out_fmt.H, out_fmt.W) < 7:
+            planes_on, why = False, "a plane is smaller than the 7 x 7 window of SSIM"
+        if not planes_on:
+            logging.info("plane metrics off (planes: null): %s", why)
+        det, cuts, scores, rels = None, [], [], []
+        if args.y4m_scene_cut > 0:
+            det = importlib.import_module("zero-tig_amd.scenecut").SceneCut(ops, dev, fmt, args.y4m_scene_cut)
+        if args.y4m_out is not None:
+            out_head = head.resized(out_fmt.W, out_fmt.H)._replace(ctag=y4m.ctag_at_depth(head.ctag, out_depth))
+            writer = y4m.Y4MWriter(args.y4m_out, out_head)
+        lpips_model = utils.lpips_model(args.lpips_weights, dev, args.lpips_precision) if args.lpips_weights else None
+        hm_on, lp_on = bool(args.hist_match), lpips_model is not None
+        npix = 3 * H * W
+
+        # the table: two device slots and two pinned host slots, used in turn
+        tab_i = [torch.zeros((CHUNK, I_COLS), dtype=torch.int64, device=dev) for _ in range(2)]
+        tab_f = [torch.zeros((CHUNK, F_COLS), dtype=torch.float64, device=dev) for _ in range(2)]
+        host_i = [torch.zeros((CHUNK, I_COLS), dtype=torch.int64).pin_memory() for _ in range(2)]
+        host_f = [torch.zeros((CHUNK, F_COLS), dtype=torch.float64).pin_memory() for _ in range(2)]
+        pending = []                               # (slot, first frame, rows, event) of chunks copied but not yet read
+        records, cut_flags = [], []
+        tot = {"psnr": 0.0, "ssim": 0.0, "lpips": 0.0, "psnr_hm": 0.0, "ssim_hm": 0.0, "lpips_hm": 0.0}
+        sse_tot, ssim_p_tot = [0, 0, 0], [0.0, 0.0, 0.0]
+
+        def lp_sum(row, c):
+            return (((row[c] + row[c + 1]) + row[c + 2]) + row[c + 3]) + row[c + 4]
+
+        def drain(keep):
+            """read every pending chunk but the newest `keep`: totals, records and the log lines"""
+            while len(pending) > keep:
+                slot, first, rows, event = pending.pop(0)
+                event.synchronize()
+                ri, rf = host_i[slot][:rows].tolist(), host_f[slot][:rows].tolist()
+                for k in range(rows):
+                    n = first + k + 1
+                    rec = {"frame": first + k, "cut": bool(cut_flags[first + k])}
+                    psnr, ssim = _psnr_of(ri[k][I_SQ], npix), rf[k][F_SSIM]
+                    tot["psnr"] += psnr
+                    tot["ssim"] += ssim
+                    rec.update(PSNR=psnr, SSIM=ssim)
+                    if not lp_on:
+                        logging.info("NUM: %d, PSNR: %.3f, SSIM: %.3f", n, psnr, ssim)
+                        logging.info("Total PSNR: %.3f, Total SSIM: %.3f", tot["psnr"] / n, tot["ssim"] / n)
+                    else:
+                        lp = lp_sum(rf[k], F_LP)
+                        tot["lpips"] += lp
+                        rec.update(LPIPS=lp)
+                        logging.info("NUM: %d, PSNR: %.3f, SSIM: %.3f, LPIPS: %.3f", n, psnr, ssim, lp)
+                        logging.info("Total PSNR: %.3f, Total SSIM: %.3f, Total LPIPS: %.3f", tot["psnr"] / n, tot["ssim"] / n, tot["lpips"] / n)
+                    if hm_on:
+                        psnr_hm, ssim_hm = _psnr_of(ri[k][I_SQ_HM], npix), rf[k][F_SSIM_HM]
+                        tot["psnr_hm"] += psnr_hm
+                        tot["ssim_hm"] += ssim_hm
+                        rec.update(PSNR_HM=psnr_hm, SSIM_HM=ssim_hm)
+                        if not lp_on:
+                            logging.info("NUM: %d, PSNR_HM: %.3f, SSIM_HM: %.3f", n, psnr_hm, ssim_hm)
+                            logging.info("Total PSNR_HM: %.3f, Total SSIM_HM: %.3f", tot["psnr_hm"] / n, tot["ssim_hm"] / n)
+                        else:
+                            lp_hm = lp_sum(rf[k], F_LP_HM)
+                            tot["lpips_hm"] += lp_hm
+                            rec.update(LPIPS_HM=lp_hm)
+                            logging.info("NUM: %d, PSNR_HM: %.3f, SSIM_HM: %.3f, LPIPS_HM: %.3f", n, psnr_hm, ssim_hm, lp_hm)
+                            logging.info("Total PSNR_HM: %.3f, Total SSIM_HM: %.3f, Total LPIPS_HM: %.3f", tot["psnr_hm"] / n,
+                                         tot["ssim_hm"] / n, tot["lpips_hm"] / n)
+                    if planes_on:
+                        sse, sp = ri[k][I_SSE:I_SSE + 3], rf[k][F_SSIM_P:F_SSIM_P + 3]
+                        for p in range(3):
+                            sse_tot[p] += sse[p]
+                            ssim_p_tot[p] += sp[p]
+                        rec.update(SSE=sse, SSIM_Y=sp[0], SSIM_U=sp[1], SSIM_V=sp[2])
+                        logging.info("NUM: %d, SSE_Y: %d, SSE_U: %d, SSE_V: %d, SSIM_Y: %.3f, SSIM_U: %.3f, SSIM_V: %.3f", n, sse[0], sse[1],
+                                     sse[2], sp[0], sp[1], sp[2])
+                    else:
+                        rec.update(SSE=None, SSIM_Y=None, SSIM_U=None, SSIM_V=None)
+                    records.append(rec)
+
+        def flush(slot, first, rows):
+            host_i[slot].copy_(tab_i[slot], non_blocking=True)
+            host_f[slot].copy_(tab_f[slot], non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+            pending.append((slot, first, rows, event))
+
+        frames, gt_frames = 0, 0
+        clock = time.perf_counter
+        t = {"decode_wait": 0.0, "step": 0.0, "metrics": 0.0, "readback": 0.0, "write": 0.0}
+        t_first = None
+        with torch.no_grad():
+            while True:
+                t0 = clock()
+                try:
+                    payload = next(reader)
+                except StopIteration:
+                    payload = None
+                try:
+                    gt_payload = next(gt_reader)
+                    gt_frames += 1
+                except StopIteration:
+                    gt_payload = None
+                if payload is None or gt_payload is None:
+                    if payload is not None or gt_payload is not None:
+                        # the longer stream is read to its end, so that the message names both lengths
+                        n_in = frames + (0 if payload is None else 1 + sum(1 for _ in reader))
+                        n_gt = gt_frames + (0 if gt_payload is None else sum(1 for _ in gt_reader))
+                        raise ValueError("the streams differ in length: --y4m_in has %d frames, --y4m_gt has %d" % (n_in, n_gt))
+                    break
+                t1 = clock()
+                t_first = t1 if t_first is None else t_first
+                is_cut = frames == 0
+                if det is not None:
+                    det.push(payload)
+                    is_cut, score, rel = det.pop()
+                    scores.append(score), rels.append(rel)
+                    if is_cut and frames:
+                        cuts.append(frames)
+                        logging.info("scene cut at frame %d: score %.4f (rel %.4f) > %g", frames, score, rel, args.y4m_scene_cut)
+                    is_cut = is_cut or frames == 0
+                cut_flags.append(det is not None and is_cut and frames > 0)
+                enhance, output, illum = step(payload, is_cut)
+                reader.release(step.loaded)
+                t2 = clock()
+                gt_t = gt.load(gt_payload)
+                gt_reader.release(gt.loaded)
+                slot, row = (frames // CHUNK) & 1, frames % CHUNK
+                ri, rf = tab_i[slot][row], tab_f[slot][row]
+                ops.sqdiff_u8(output, gt_t, out=ri[I_SQ:I_SQ + 1])
+                ops.ssim_u8_dev(output, gt_t, out=rf[F_SSIM:F_SSIM + 1])
+                if lp_on:
+                    gt_feat = lpips_model.features(gt_t)
+                    lpips_model.distance_dev(lpips_model.features(output), gt_feat, rf[F_LP:F_LP + 5])
+                if hm_on:
+                    hm = utils.histogram_match(output, gt_t)
+                    ops.sqdiff_u8(hm, gt_t, out=ri[I_SQ_HM:I_SQ_HM + 1])
+                    ops.ssim_u8_dev(hm, gt_t, out=rf[F_SSIM_HM:F_SSIM_HM + 1])
+                    if lp_on:
+                        lpips_model.distance_dev(lpips_model.features(hm), gt_feat, rf[F_LP_HM:F_LP_HM + 5])
+                if planes_on:
+                    ops.yuv_sse(step.yuv[1], gt.payload, out_fmt, out=ri[I_SSE:I_SSE + 3])
+                    for p in range(3):
+                        ops.ssim_plane(step.yuv[1], gt.payload, out_fmt, p, out=rf[F_SSIM_P + p:F_SSIM_P + p + 1])
+                t3 = clock()
+                if writer is not None:
+                    writer.submit(step.yuv[0])
+                t4 = clock()
+                frames += 1
+                if frames % CHUNK == 0:
+                    flush(slot, frames - CHUNK, CHUNK)
+                    drain(1)
+                t5 = clock()
+                t["decode_wait"] += t1 - t0
+                t["step"] += t2 - t1
+                t["metrics"] += t3 - t2
+                t["write"] += t4 - t3
+                t["readback"] += t5 - t4
+            t5 = clock()
+            if frames % CHUNK:
+                flush((frames // CHUNK) & 1, frames - frames % CHUNK, frames % CHUNK)
+            drain(0)
+            t_end = clock()                        # every metric of the last frame has been read back
+            t["readback"] += t_end - t5
+    finally:
+        errors = []
+        if writer is not None:
+            try:
+                writer.close()
+            except BaseException as e:             # noqa: BLE001
+                errors.append(e)
+        reader.close()
+        gt_reader.close()
+        if errors and sys.exc_info()[0] is None:
+            raise errors[0]
+    n = max(frames, 1)
+    planes = None
+    if planes_on:
+        hc, wc = out_fmt.chroma_shape
+        samples = [out_fmt.H * out_fmt.W, hc * wc, hc * wc]
+        m = (1 << out_fmt.depth) - 1
+        planes = {"depth": out_fmt.depth, "ss": out_fmt.ss, "samples": samples, "SSE": sse_tot}
+        for p, name in enumerate("YUV"):
+            planes["PSNR_" + name] = 10.0 * math.log10(m * m * samples[p] * frames / sse_tot[p]) if sse_tot[p] else None
+        for p, name in enumerate("YUV"):
+            planes["SSIM_" + name] = ssim_p_tot[p] / n
+    result = {"Total_PSNR": tot["psnr"] / n, "Total_SSIM": tot["ssim"] / n, "Total_LPIPS": tot["lpips"] / n if lp_on else None,
+              "Total_PSNR_HM": tot["psnr_hm"] / n if hm_on else None, "Total_SSIM_HM": tot["ssim_hm"] / n if hm_on else None,
+              "Total_LPIPS_HM": tot["lpips_hm"] / n if lp_on and hm_on else None, "images": frames, "planes": planes}
+    if det is not None:
+        result["cuts"] = cuts
+    with open(os.path.join(args.save, "Metrics.json"), "w") as fh:
+        json.dump(result, fh)
+    if args.y4m_frames_json:
+        with open(args.y4m_frames_json, "w") as fh:
+            json.dump(records, fh)
+    if args.y4m_cuts_json:
+        with open(args.y4m_cuts_json, "w") as fh:
+            json.dump({"threshold": args.y4m_scene_cut, "cuts": cuts, "score": scores, "rel": rels}, fh)
+    if args.timing_json and frames:
+        per = {k + "_ms": 1e3 * v / frames for k, v in t.items()}
+        with open(args.timing_json, "w") as fh:
+            json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), graph=args.graph, y4m=1,
+                           hist_match=int(hm_on), lpips=int(lp_on), planes=int(planes_on),
+                           scene_wait_ms=1e3 * det.wait / frames if det is not None else None), fh)
+    logging.info("Total frame number: %d", frames)
 
 
 def main():
     args = parser.parse_args()
+    if check_y4m_args(args):
+        return main_y4m(args)
+    if args.save_images is None:
+        args.save_images = 20
     os.makedirs(args.save, exist_ok=True)
     logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(asctime)s %(message)s", datefmt="%m/%d %I:%M:%S %p")
     logging.getLogger().addHandler(logging.FileHandler(os.path.join(args.save, "log.txt")))

@@ -376,6 +376,28 @@ int zt_luma_grid_u16(const uint16_t* y, int H, int W, int depth, int yo8, unsign
 int zt_luma_grid_u8(const unsigned char* y, int H, int W, int yo, unsigned int* grid /* [gh*gw] */, zt_stream_t stream);
 int zt_grid_sad_u32(const unsigned int* a, const unsigned int* b, int n, unsigned long long* out2 /* sad, tot */, zt_stream_t stream);
 
+/* ---- plane metrics of a raw video stream (zt_planes.hip): evals.py --y4m_in / --y4m_gt, DESIGN 8h ----------------------------------
+ * Samples as in the zt_yuv blocks: depth 8 = uint8; depth B in {9, 10, 12, 14, 16} = little-endian uint16 (2-byte aligned), a
+ * sample above m = 2^B - 1 is read as m.  Any other depth: ZT_EINVAL.  Results go to device memory; nothing synchronises.
+ * zt_yuv_sse: a, b = two payloads of ONE layout (planes Y, U, V with the shapes above for ss in {420, 422, 444}; W even for 420 /
+ *   422, H even for 420, anything else ZT_EINVAL); out3[p] = sum over plane p of (a - b)^2 as exact 64-bit integers, in one pass
+ *   over both payloads.  A squared difference is below 2^32, so a plane of fewer than 2^31 samples cannot wrap 64 bits: a frame of
+ *   H * W >= 2^31 is ZT_EINVAL.  PSNR_p = 10 log10(m^2 n_p / out3[p]).  16-byte loads when W % 8 == 0 (W % 16 == 0 at 8 bits) and
+ *   both pointers are 16-byte aligned, sample-wide loads otherwise, same result.  partial: 3 * nblk x 8 bytes of workspace,
+ *   1 <= nblk <= 4096 workgroups share the samples.
+ * zt_ssim_plane: out[0] = skimage structural_similarity(a, b, data_range=m) of two contiguous planes [H][W] (a plane pointer inside
+ *   a payload is fine): the definition of zt_ssim_u8_f32 for one channel -- 7x7 uniform window, sample covariance (49/48),
+ *   C1 = (0.01 m)^2, C2 = (0.03 m)^2, 3-sample border cropped, mean over the windows inside the plane.  The five window sums are
+ *   exact integers (32-bit up to 12 bits, 49 * 4095^2 < 2^30; 64-bit for 14 and 16 bits), the rest is fp64 in a fixed order.
+ *   16-byte loads when W % 8 == 0 (W % 16 == 0 at 8 bits) and both pointers are 16-byte aligned, sample-wide loads otherwise, same
+ *   result.  partial: npartial x 8 bytes of workspace, npartial >= ceil((H-6)/TH) * ceil((W-6)/64), TH = 32 rows up to 12 bits and 16
+ *   rows for 14 and 16 bits (ceil((H-6)/16) * ceil((W-6)/64) is enough at every depth).  H < 7 or W < 7: ZT_EINVAL.
+ * Integer where stated and deterministic (no atomics, fixed reduction order): same input, same bits. */
+int zt_yuv_sse(const void* a, const void* b, int H, int W, int ss, int depth, unsigned long long* partial, int nblk,
+               unsigned long long* out3 /* Y, U, V */, zt_stream_t stream);
+int zt_ssim_plane(const void* a, const void* b, int H, int W, int depth, double* partial, int npartial, double* out,
+                  zt_stream_t stream);
+
 /* ---- result PNGs encoded on the device (zt_png.hip) ------------------------------------------------------------------
  * predict.py:57-61, 101-104 (and evals.py's --save_images files): `Image.fromarray(u8).save(path, "PNG")`.  src: uint8 [H][W][3] (what
  * zt_quantize_u8_hwc writes) -> out: a complete zlib stream (78 01, deflate blocks, big-endian Adler-32) of the Paeth-filtered

@@ -1,0 +1,219 @@
+#!/usr/bin/env python3
+"""GPU box: what grading a raw video costs (evals.py --y4m_in / --y4m_gt).  One MI355X, at most 16 CPUs.
+
+(a) kernels: HIP-event median over --reps calls of the two entry points of zt_planes.hip alone on a 1080p C420 pair, at 8 and at
+    10 bits: `Ops.yuv_sse` on the whole payloads, `Ops.ssim_plane` on the luma plane and on one chroma plane, each with 16-byte
+    loads and, from a payload one sample off a 16-byte boundary, with sample-wide loads; the bytes each call reads and the rate.
+(b) end to end: a synthetic 1080p C420mpeg2 pair (--frames frames, --distinct different ones; low-light and clean twin of
+    zero-tig_amd/synth.py through the host encoder of zero-tig_amd/y4m.py), --repeats runs each, the runs of the settings alternating:
+      predict        predict.py --graph 1 --precision bf16 --y4m_in LOW (two Y4M streams written): the loop evals.py extends
+      evals          evals.py   --graph 1 --precision bf16 --y4m_in LOW --y4m_gt GT --hist_match 0 (PSNR, SSIM, the plane metrics)
+      evals_hm       the same with histogram matching on (PSNR_HM, SSIM_HM)
+      evals_lpips    the same as `evals` with --lpips_weights (synthetic VGG weights, seeded) --lpips_precision bf16
+    frames per second and the host-side split per frame from each script's --timing_json.
+
+This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
+ends the run.  Writes the JSON to --out and prints it as one line.
+Usage: python tools/bench_evals_y4m.py [--frames 256] [--out profiles/evals_y4m_1080p.json]"""
+import argparse
+import importlib
+import json
+import math
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+H, W = 1080, 1920
+
+
+# ---- child: the two entry points alone -------------------------------------------------------------------------------------------
+def kernels_mode(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("zero-tig_amd.lib").get_lib()               # raises without a HIP device
+    ops = importlib.import_module("zero-tig_amd.ops").Ops(lib)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    y4m = importlib.import_module("zero-tig_amd.y4m")
+    out = {"format": "1080x1920 C420, limited, bt709: payloads of the low-light frame 3 (x 4, clipped) and its clean twin"}
+    low = np.clip(np.transpose(np.asarray(synth.lowlight_frame(3, H, W))[0], (1, 2, 0)).astype(np.float64) * 4.0, 0.0, 1.0)
+    clean = np.transpose(np.asarray(synth.clean_frame(3, H, W)).reshape(3, H, W), (1, 2, 0)).astype(np.float64)
+
+    def shifted(p, es):                             # the same bytes one sample behind a 16-byte boundary
+        buf = torch.empty(p.numel() + 16, dtype=torch.uint8, device="cuda")
+        view = buf[es:es + p.numel()]
+        view.copy_(p)
+        return view
+    for depth in (8, 10):
+        fmt = y4m.YuvFormat(W, H, 420, 1, "bt709", 0, depth)
+        if depth == 8:
+            pay = [y4m.encode_host((x * 255.0 + 0.5).astype(np.uint8), fmt) for x in (low, clean)]
+        else:
+            pay = [y4m.encode_host((x * 65535.0 + 0.5).astype(np.uint16), fmt) for x in (low, clean)]
+        es = 2 if depth > 8 else 1
+        pa, pb = (torch.from_numpy(p).cuda() for p in pay)
+        sa, sb = shifted(pa, es), shifted(pb, es)
+        sse3 = torch.empty(3, dtype=torch.int64, device="cuda")
+        one = torch.empty(1, dtype=torch.float64, device="cuda")
+        hc, wc = fmt.chroma_shape
+        calls = {"yuv_sse": (lambda: ops.yuv_sse(pa, pb, fmt, out=sse3), 2 * fmt.frame_bytes),
+                 "yuv_sse_sample_loads": (lambda: ops.yuv_sse(sa, sb, fmt, out=sse3), 2 * fmt.frame_bytes),
+                 "ssim_plane_Y": (lambda: ops.ssim_plane(pa, pb, fmt, 0, out=one), 2 * es * H * W),
+                 "ssim_plane_Y_sample_loads": (lambda: ops.ssim_plane(sa, sb, fmt, 0, out=one), 2 * es * H * W),
+                 "ssim_plane_U": (lambda: ops.ssim_plane(pa, pb, fmt, 1, out=one), 2 * es * hc * wc)}
+        row = {"payload_bytes": fmt.frame_bytes}
+        for name, (fn, read) in calls.items():
+            for _ in range(5):
+                fn()
+            torch.cuda.synchronize()
+            ms = []
+            for _ in range(a.reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            med = statistics.median(ms)
+            row[name] = {"ms": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "bytes_read": read,
+                         "gbs": round(read / med / 1e6, 1)}
+            print("[bench_evals_y4m] %d-bit %s %s" % (depth, name, row[name]), file=sys.stderr, flush=True)
+        ref = ops.yuv_sse(pa, pb, fmt).tolist()
+        assert ops.yuv_sse(sa, sb, fmt).tolist() == ref, "the sample-wide and the 16-byte path disagree"
+        assert ops.ssim_plane(pa, pb, fmt, 0).item() == ops.ssim_plane(sa, sb, fmt, 0).item()
+        m = (1 << depth) - 1
+        row["sse"] = ref
+        row["psnr_y"] = 10.0 * math.log10(m * m * H * W / ref[0])
+        row["ssim_y"] = ops.ssim_plane(pa, pb, fmt, 0).item()
+        out["depth_%d" % depth] = row
+    with open(a.json, "w") as fh:
+        json.dump(out, fh)
+
+
+# ---- driver ---------------------------------------------------------------------------------------------------------------------
+def _one_pair(t):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    y4m = importlib.import_module("zero-tig_amd.y4m")
+    fmt = y4m.YuvFormat(W, H, 420, 1, "bt709", 0)
+    out = []
+    for fn in (synth.lowlight_frame, synth.clean_frame):
+        x = np.asarray(fn(t, H, W), dtype=np.float32).reshape(3, H, W)
+        out.append(y4m.encode_host((np.transpose(x, (1, 2, 0)) * 255.0 + 0.5).astype(np.uint8), fmt))
+    return out
+
+
+def make_pair(tmp, frames, distinct):
+    """LOW.y4m / GT.y4m: `distinct` synthetic frame pairs encoded once, written round-robin; weights from synth.make_state(3) and a
+    seeded synthetic LPIPS state dict"""
+    import multiprocessing as mp
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    y4m = importlib.import_module("zero-tig_amd.y4m")
+    lp = importlib.import_module("zero-tig_amd.lpips")
+    with mp.get_context("spawn").Pool(min(8, distinct)) as pool:
+        pairs = pool.map(_one_pair, range(distinct))
+    head = y4m.Header(W, H, "30:1", "p", None, "420mpeg2", "LIMITED")
+    files = {}
+    for k, name in enumerate(("low", "gt")):
+        files[name] = os.path.join(tmp, name + ".y4m")
+        y4m.write_file(files[name], head, [pairs[i % distinct][k] for i in range(frames)])
+    files["weights"] = os.path.join(tmp, "weights.pt")
+    torch.save({k: torch.from_numpy(np.array(v)) for k, v in synth.make_state(3).items()}, files["weights"])
+    g = torch.Generator().manual_seed(0)
+    sd = {}
+    for idx, (cin, cout) in zip(lp.CONV_IDX, lp.CONV_CH):
+        sd["features.%d.weight" % idx] = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
+        sd["features.%d.bias" % idx] = torch.randn(cout, generator=g) * 0.05
+    for k, c in enumerate(lp.TAP_CH):
+        sd["lin%d.model.1.weight" % k] = torch.rand(1, c, 1, 1, generator=g) / c
+    files["lpips"] = os.path.join(tmp, "lpips_vgg.pt")
+    torch.save(sd, files["lpips"])
+    return files
+
+
+def gpu_step(cmd, limit, env=None):
+    """one GPU child under its own time limit; a failure ends the whole run"""
+    t0 = time.perf_counter()
+    r = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=ROOT, env=env, capture_output=True, text=True)
+    dt = time.perf_counter() - t0
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout[-3000:] + r.stderr[-3000:])
+        raise SystemExit("[bench_evals_y4m] step failed with status %d, stopping: %s" % (r.returncode, " ".join(cmd)))
+    return dt
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels"])
+    ap.add_argument("--json", type=str, default=None)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--frames", type=int, default=256)
+    ap.add_argument("--distinct", type=int, default=8)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--settings", type=str, nargs="*", default=["predict", "evals", "evals_hm", "evals_lpips"],
+                    choices=["predict", "evals", "evals_hm", "evals_lpips"])
+    ap.add_argument("--skip-kernels", action="store_true", help="part (b) only")
+    ap.add_argument("--step-timeout", type=int, default=240)
+    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "evals_y4m_1080p.json"))
+    a = ap.parse_args()
+    if a.mode == "kernels":
+        return kernels_mode(a)
+    out = {"what": "evals.py --y4m_in / --y4m_gt next to predict.py --y4m_in, --graph 1 --precision bf16, over one synthetic 1080p "
+                   "C420mpeg2 pair of %d frames (%d distinct), %d runs per setting, the runs alternating, one session on one box; fps "
+                   "and the host-side split per frame from each script's --timing_json (predict: first frame read to last stream "
+                   "closed, two Y4M streams written; evals: first frame read to the last metric read back, nothing written); "
+                   "evals = --hist_match 0, no LPIPS; evals_hm = histogram matching on; evals_lpips = --hist_match 0 with a seeded "
+                   "synthetic VGG state dict, --lpips_precision bf16; kernels = Ops.yuv_sse / Ops.ssim_plane alone, HIP-event median "
+                   "of %d calls" % (a.frames, a.distinct, a.repeats, a.reps), "cpus": len(os.sched_getaffinity(0))}
+    tmp = tempfile.mkdtemp(prefix="zt_bench_evals_y4m_")
+    try:
+        if not a.skip_kernels:
+            kj = os.path.join(tmp, "kernels.json")
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "kernels", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
+            out["kernels"] = json.load(open(kj))
+        files = make_pair(tmp, a.frames, a.distinct)
+        env = dict(os.environ, PYTHONPATH=ROOT)
+        common = ["--model_pretrain", files["weights"], "--graph", "1", "--precision", "bf16", "--y4m_in", files["low"]]
+        extra = {"predict": [], "evals": ["--y4m_gt", files["gt"], "--hist_match", "0"], "evals_hm": ["--y4m_gt", files["gt"]],
+                 "evals_lpips": ["--y4m_gt", files["gt"], "--hist_match", "0", "--lpips_weights", files["lpips"], "--lpips_precision", "bf16"]}
+        loops, wall = {s: [] for s in a.settings}, {s: [] for s in a.settings}
+        for rep in range(a.repeats):
+            for s in a.settings:
+                save, tj = os.path.join(tmp, "out_" + s), os.path.join(tmp, "timing_%s.json" % s)
+                cmd = [sys.executable, "predict.py" if s == "predict" else "evals.py"] + common + extra[s] + ["--save", save, "--timing_json", tj]
+                wall[s].append(gpu_step(cmd, a.step_timeout, env=env))
+                loops[s].append(json.load(open(tj)))
+                if s != "predict" and rep == 0:
+                    out.setdefault("metrics", {})[s] = json.load(open(os.path.join(save, "Metrics.json")))
+                shutil.rmtree(save, ignore_errors=True)
+                print("[bench_evals_y4m] %s run %d: %.1f s wall, %.2f fps" % (s, rep, wall[s][-1], loops[s][-1]["fps"]), file=sys.stderr, flush=True)
+        out["end_to_end"] = {}
+        for s in a.settings:
+            fps = [l["fps"] for l in loops[s]]
+            out["end_to_end"][s] = {"fps_runs": [round(v, 2) for v in fps], "fps_median": round(statistics.median(fps), 2),
+                                    "fps_spread": round(max(fps) - min(fps), 2), "ms_per_frame_median": round(1e3 / statistics.median(fps), 3),
+                                    "loop": sorted(loops[s], key=lambda l: l["fps"])[len(fps) // 2], "wall_s": [round(v, 2) for v in wall[s]]}
+        if "predict" in a.settings:
+            base = out["end_to_end"]["predict"]["ms_per_frame_median"]
+            for s in a.settings:
+                out["end_to_end"][s]["ms_per_frame_over_predict"] = round(out["end_to_end"][s]["ms_per_frame_median"] - base, 3)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

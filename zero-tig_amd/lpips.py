@@ -89,5 +89,13 @@ class LpipsVGG:
         d = [float(v) for v in out.cpu().tolist()]
         return ((((d[0] + d[1]) + d[2]) + d[3]) + d[4]), d
 
+    def distance_dev(self, fa, fb, out5):
+        """[d_1 .. d_5] of `distance` into `out5` (float64 [5] on the device, e.g. part of a table row); no read-back.  The
+        caller's LPIPS is (((d_1 + d_2) + d_3) + d_4) + d_5, the order `distance` adds them in."""
+        assert out5.dtype == torch.float64 and tuple(out5.shape) == (5,) and out5.is_contiguous(), (out5.dtype, tuple(out5.shape))
+        for l in range(5):
+            self.ops.lpips_layer(fa[l], fb[l], self.lin[l], out5[l:l + 1])
+        return out5
+
     def __call__(self, a, b):
         return self.distance(self.features(a), self.features(b))[0]

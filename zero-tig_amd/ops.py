@@ -429,6 +429,84 @@ class Ops:
         self.lib.call("zt_grid_sad_u32", a, b, a.numel(), out, self._s(a))
         return out
 
+    # ---- plane metrics of two payloads (zt_planes.hip) ---------------------------------------------------
+    def _plane_ws(self, fmt, dev):
+        """the workspaces of `yuv_sse` / `ssim_plane` for one layout on one device, allocated once: {"sse": int64 [3 * nblk],
+        "nblk", "ssim": float64 [npartial] (sized for the luma plane at the smaller tile), "npartial"}"""
+        cache = self.__dict__.setdefault("_plane_workspaces", {})
+        key = (fmt.W, fmt.H, fmt.ss, fmt.depth, str(dev))
+        if key not in cache:
+            hc, wc = fmt.chroma_shape
+            nblk = max(1, min(1024, (fmt.H * fmt.W + 2 * hc * wc) // 8192))
+            npartial = max(1, -(-(fmt.H - 6) // 16)) * max(1, -(-(fmt.W - 6) // 64))
+            cache[key] = {"sse": torch.empty(3 * nblk, dtype=torch.int64, device=dev), "nblk": nblk,
+                          "ssim": torch.empty(npartial, dtype=torch.float64, device=dev), "npartial": npartial}
+        return cache[key]
+
+    def yuv_sse(self, pa, pb, fmt, out=None):
+        """two Y4M payloads of `fmt` (1-D uint8, `fmt.frame_bytes` each) -> int64 [3] on the device: per plane (Y, U, V) the sum of
+        the squared sample differences at the format's depth, exact (a deep sample above 2^depth - 1 counts as 2^depth - 1).
+        Nothing synchronises; `out` (int64 [3], e.g. a row of a table) is overwritten."""
+        self._yuv_payload(pa, fmt), self._yuv_payload(pb, fmt)
+        assert pa.device == pb.device, (pa.device, pb.device)
+        if out is None:
+            out = torch.empty(3, dtype=torch.int64, device=pa.device)
+        assert tuple(out.shape) == (3,) and out.dtype == torch.int64 and out.is_contiguous() and out.device == pa.device
+        ws = self._plane_ws(fmt, pa.device)
+        self.lib.call("zt_yuv_sse", pa, pb, fmt.H, fmt.W, fmt.ss, fmt.depth, ws["sse"], ws["nblk"], out, self._s(pa))
+        return out
+
+    def ssim_plane(self, pa, pb, fmt, plane, out=None):
+        """plane 0 / 1 / 2 (Y, U, V) of two Y4M payloads of `fmt` -> float64 [1] on the device: skimage's
+        structural_similarity(a, b, data_range=2^depth - 1) of that plane (7x7 uniform window; the plane must be at least 7 x 7).
+        Nothing synchronises; `out` (float64 [1], e.g. a cell of a table) is overwritten."""
+        self._yuv_payload(pa, fmt), self._yuv_payload(pb, fmt)
+        assert pa.device == pb.device and plane in (0, 1, 2), (pa.device, pb.device, plane)
+        hc, wc = fmt.chroma_shape
+        es = 2 if fmt.depth > 8 else 1
+        H, W = (fmt.H, fmt.W) if plane == 0 else (hc, wc)
+        off = es * (0 if plane == 0 else fmt.H * fmt.W + (plane - 1) * hc * wc)
+        if out is None:
+            out = torch.empty(1, dtype=torch.float64, device=pa.device)
+        assert out.numel() == 1 and out.dtype == torch.float64 and out.is_contiguous() and out.device == pa.device
+        ws = self._plane_ws(fmt, pa.device)
+        self.lib.call("zt_ssim_plane", pa.data_ptr() + off, pb.data_ptr() + off, H, W, fmt.depth, ws["ssim"], ws["npartial"], out,
+                      self._s(pa))
+        return out
+
+    # ---- evals.py's frame metrics, results left on the device (the video loop reads a table back every 64 frames) -------
+    def sqdiff_u8(self, a, b, out=None):
+        """the integer of `psnr_u8`: sum (round(a*255) - round(b*255))^2 -> int64 [1] on the device, no read-back"""
+        _f32c(a), _f32c(b)
+        n = a.numel()
+        assert b.numel() == n
+        ws = self.__dict__.setdefault("_sqdiff_workspaces", {})
+        nblk = max(1, min(1024, n // 4096))
+        key = (nblk, str(a.device))
+        if key not in ws:
+            ws[key] = torch.empty(nblk, dtype=torch.int64, device=a.device)
+        if out is None:
+            out = torch.empty(1, dtype=torch.int64, device=a.device)
+        assert out.numel() == 1 and out.dtype == torch.int64 and out.is_contiguous() and out.device == a.device
+        self.lib.call("zt_sqdiff_u8_f32", a, b, n, ws[key], nblk, out, self._s(a))
+        return out
+
+    def ssim_u8_dev(self, a, b, out=None):
+        """the number of `ssim_u8` -> float64 [1] on the device, no read-back"""
+        _f32c(a), _f32c(b)
+        assert a.dim() == 4 and a.shape[0] == 1 and a.shape[1] == 3 and a.shape == b.shape, (a.shape, b.shape)
+        H, W = int(a.shape[2]), int(a.shape[3])
+        npart = 3 * max(1, -(-(H - 6) // 32)) * max(1, -(-(W - 6) // 64))
+        ws = self.__dict__.setdefault("_ssim_workspaces", {})
+        key = (npart, str(a.device))
+        if key not in ws:
+            ws[key] = torch.empty(npart, dtype=torch.float64, device=a.device)
+        if out is None:
+            out = torch.empty(1, dtype=torch.float64, device=a.device)
+        assert out.numel() == 1 and out.dtype == torch.float64 and out.is_contiguous() and out.device == a.device
+        self.lib.call("zt_ssim_u8_f32", a, b, H, W, ws[key], npart, out, self._s(a))
+        return out
+
     def psnr_u8(self, a, b):
         """evals.py:83-85: cv2.PSNR of round(a*255), round(b*255) -> python float (inf when identical); one 8-byte read-back."""
         _f32c(a), _f32c(b)
