@@ -94,7 +94,9 @@ int zt_repack_conv_weight_f32(const float* src, float* dst, int Cout, int Cin, i
 /* per-(n,c) partial sums over HW pixels: partial[((n*nblk+blk)*2 + {0 sum, 1 sum of squares})*C + c] */
 int zt_chan_stats_nhwc(const void* x, int dt, int ldx, int N, int HW, int C, int nblk, float* partial, zt_stream_t stream);
 /* mode 0 instance norm (scale = rstd, shift = -mean*rstd); 1 train BN (batch stats, running stats += momentum update with
- * unbiased variance, *num_batches_tracked += 1); 2 eval BN (running stats).  Outputs scale/shift (and mean/rstd) [N][C]. */
+ * unbiased variance, *num_batches_tracked += 1); 2 eval BN (running stats).  Outputs scale/shift (and mean/rstd) [N][C].
+ * Requires N, C, count > 0; modes 0 and 1 read partial and need nblk > 0 (mode 2 ignores both: partial may be NULL);
+ * mode 1 needs N == 1 and count > 1 (the unbiased variance of one value per channel is undefined: torch raises). */
 int zt_norm_finalize_f32(const float* partial, int nblk, int N, int C, long long count, float eps, int mode,
                          const float* gamma, const float* beta, float* running_mean, float* running_var,
                          long long* num_batches_tracked, float momentum, float* scale, float* shift, float* mean_out,
@@ -109,7 +111,9 @@ int zt_norm_apply_nhwc(const void* x, int dt, int ldx, const float* scale, const
                            void* y, int ldy, int N, int HW, int C, int inner_relu, int outer_relu, zt_stream_t stream);
 /* backward of y = ReLU(BN_train(z)): stage 1 partial sums of dyh = dy*[bn>0] and dyh*zhat; generic partial reduction;
  * stage 2 dz = gamma*rstd*(dyh - mean(dyh) - zhat*mean(dyh*zhat)) with sums = [sum dyh (C) | sum dyh*zhat (C)];
- * eval_mode = 1: statistics are constants (running stats): dz = gamma*rstd*dyh (reference epochs >= 1, train.py:138) */
+ * eval_mode = 1: statistics are constants (running stats): dz = gamma*rstd*dyh (reference epochs >= 1, train.py:138).
+ * zt_bn_bwd_reduce and zt_bn_bwd_apply require what zt_chan_stats_nhwc does: C % 4 == 0, C >= 4 (reduce: C <= 1024), every
+ * ld % 4 == 0, HW > 0, 8-byte aligned dy / z / dz, non-NULL scale / shift / mean / rstd; reduce also nblk > 0. */
 int zt_bn_bwd_reduce(const void* dy, int dt, int lddy, const void* z, int ldz, const float* scale, const float* shift,
                          const float* mean, const float* rstd, int HW, int C, int nblk, float* partial, zt_stream_t stream);
 int zt_partial_reduce_f32(const float* partial, int nblk, int stride, int n, float* out, int accumulate, float* out2,

@@ -567,6 +567,8 @@ extern "C" int zt_norm_finalize_f32(const float* partial, int nblk, int N, int C
   ZT_REQUIRE(scale && shift && (mode == 2 || partial) && (mode == 0 || (gamma && beta)));
   ZT_REQUIRE(mode == 0 || (running_mean && running_var));
   ZT_REQUIRE(mode != 1 || N == 1);
+  ZT_REQUIRE(mode >= 0 && mode <= 2 && N > 0 && C > 0 && count > 0 && (mode == 2 || nblk > 0));
+  ZT_REQUIRE(mode != 1 || count > 1);                           // unbiased variance: torch raises on one value per channel
   hipLaunchKernelGGL(norm_finalize_kernel, dim3(N), dim3(1024), 0, stream, partial, nblk, C, (double)count, eps, mode, gamma,
                      beta, running_mean, running_var, num_batches_tracked, momentum, scale, shift, mean_out, rstd_out);
   ZT_LAUNCH_CHECK();
@@ -597,7 +599,8 @@ extern "C" int zt_norm_apply_nhwc(const void* x, int dt, int ldx, const float* s
 extern "C" int zt_bn_bwd_reduce(const void* dy, int dt, int lddy, const void* z, int ldz, const float* scale,
                                 const float* shift, const float* mean, const float* rstd, int HW, int C, int nblk,
                                 float* partial, hipStream_t stream) {
-  ZT_REQUIRE(dy && z && partial && C % 4 == 0 && C <= 1024);
+  ZT_REQUIRE(dy && z && partial && C % 4 == 0 && C >= 4 && C <= 1024 && lddy % 4 == 0 && ldz % 4 == 0 && nblk > 0 && HW > 0);
+  ZT_REQUIRE(scale && shift && mean && rstd && (((uintptr_t)dy | (uintptr_t)z) & 7) == 0);
   if (dt != 0 && HW >= 4096 && zt_x8_ok(dy, lddy, C) && zt_x8_ok(z, ldz, C))
     hipLaunchKernelGGL(stats_bf16x8_kernel<1>, dim3(nblk, 1), dim3(256), 0, stream, (const zt_bf16*)z, ldz, (const zt_bf16*)dy, lddy, scale,
                        shift, mean, rstd, HW, C, nblk, partial, NormTail{});
@@ -655,7 +658,8 @@ extern "C" int zt_bn_bwd_sums_centered_f32(const float* partial, int nblk, int C
 extern "C" int zt_bn_bwd_apply(const void* dy, int dt, int lddy, const void* z, int ldz, const float* scale,
                                const float* shift, const float* mean, const float* rstd, const float* sums,
                                void* dz, int lddz, int HW, int C, int eval_mode, hipStream_t stream) {
-  ZT_REQUIRE(dy && z && dz && sums && C % 4 == 0);
+  ZT_REQUIRE(dy && z && dz && sums && C % 4 == 0 && C >= 4 && lddy % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0 && HW > 0);
+  ZT_REQUIRE(scale && shift && mean && rstd && (((uintptr_t)dy | (uintptr_t)z | (uintptr_t)dz) & 7) == 0);
   long long total4 = (long long)HW * (C / 4);
   if (dt != 0 && HW >= 4096 && zt_x8_ok(dy, lddy, C) && zt_x8_ok(z, ldz, C) && zt_x8_ok(dz, lddz, C)) {
     const int npg = zt_cdiv(HW, NPIX);
