@@ -68,16 +68,35 @@ parser.add_argument("--timing_json", type=str, default=None,
                          "read-backs, writer) and its frames per second to this file")
 parser.add_argument("--y4m_frames_json", type=str, default=None,
                     help="write one record per frame here (plane SSEs and SSIMs, the RGB metrics, the cut flag); needs --y4m_in")
+parser.add_argument("--tc", type=int, default=0, choices=[0, 1],
+                    help="1: temporal consistency (DESIGN 8i): per frame pair of a sequence the warping error (Lai et al. 2018, occlusion "
+                         "test of Ruder et al. 2016), the plain frame difference and MABD (Jiang and Zheng 2019) of the denoise result, "
+                         "next to the same numbers of the ground truth; flows from RAFT on the ground-truth frames; needs --y4m_in")
+parser.add_argument("--tc_scale", type=int, default=None,
+                    help="integer S >= 1: the temporal metrics are taken at (H // S, W // S); default --of_scale; needs --tc 1")
+parser.add_argument("--tc_raft_weights", type=str, default=None,
+                    help="a RAFT state dict in the reference's key names (a module. prefix is accepted) for the flows of --tc 1, e.g. "
+                         "trained RAFT weights of your own.  Default: the raft.* tensors of the model as --model_pretrain leaves them; as "
+                         "in the reference, RAFT is never trained there and is built after the weights file is read, so unless your "
+                         "checkpoint was made to hold a trained RAFT these are freshly drawn weights (seeded by --seed) and the warping "
+                         "error measures little; needs --tc 1")
 
 CHUNK = 64                                         # frames per read-back of the metric table
 # columns of the metric table's two halves: int64 (exact sums) and float64
 I_SSE, I_SQ, I_SQ_HM, I_COLS = 0, 3, 4, 5
 F_SSIM, F_SSIM_HM, F_SSIM_P, F_LP, F_LP_HM, F_COLS = 0, 1, 2, 5, 10, 15
+I_TC, F_TC = I_COLS, F_COLS                        # --tc 1: two more integers and six more doubles behind them
 
 
 def check_y4m_args(args):
     """every argument check of the video mode, before anything touches the device -> True when the video mode was asked for"""
+    if not args.tc:
+        for flag in ("tc_scale", "tc_raft_weights"):
+            if getattr(args, flag) is not None:
+                parser.error("--%s needs --tc 1" % flag)
     if args.y4m_in is None:
+        if args.tc:
+            parser.error("--tc 1 needs --y4m_in")
         for flag in ("y4m_gt", "y4m_out", "y4m_size", "y4m_cuts_json", "y4m_frames_json", "timing_json"):
             if getattr(args, flag) is not None:
                 parser.error("--%s needs --y4m_in" % flag)
@@ -109,6 +128,13 @@ def check_y4m_args(args):
         parser.error("--y4m_cuts_json needs --y4m_scene_cut T (T > 0) and --y4m_in")
     if not os.path.isfile(args.y4m_gt):
         parser.error("--y4m_gt %s: no such file" % args.y4m_gt)
+    if args.tc:
+        if args.tc_scale is None:
+            args.tc_scale = args.of_scale
+        if args.tc_scale < 1:
+            parser.error("--tc_scale is an integer >= 1; got %d" % args.tc_scale)
+        if args.tc_raft_weights is not None and not os.path.isfile(args.tc_raft_weights):
+            parser.error("--tc_raft_weights %s: no such file" % args.tc_raft_weights)
     return True
 
 
@@ -186,6 +212,18 @@ def main_y4m(args):
             planes_on, why = False, "a plane is smaller than the 7 x 7 window of SSIM"
         if not planes_on:
             logging.info("plane metrics off (planes: null): %s", why)
+        tc, tc_flags = None, []
+        if args.tc:
+            temporal = importlib.import_module("zero-tig_amd.temporal")
+            why = temporal.too_small(H, W, args.tc_scale)
+            if why is not None:
+                logging.info("temporal metrics off (temporal: null): %s", why)
+            else:
+                if args.tc_raft_weights is not None:
+                    raft_w = temporal.load_raft_weights(args.tc_raft_weights, model.raft.state_dict(), dev)
+                else:
+                    raft_w = {"raft." + k: v.data for k, v in model.raft.state_dict().items()}
+                tc = temporal.TemporalConsistency(ops, raft_w, dev, H, W, args.tc_scale, model.precision)
         det, cuts, scores, rels = None, [], [], []
         if args.y4m_scene_cut > 0:
             det = importlib.import_module("zero-tig_amd.scenecut").SceneCut(ops, dev, fmt, args.y4m_scene_cut)
@@ -197,14 +235,17 @@ def main_y4m(args):
         npix = 3 * H * W
 
         # the table: two device slots and two pinned host slots, used in turn
-        tab_i = [torch.zeros((CHUNK, I_COLS), dtype=torch.int64, device=dev) for _ in range(2)]
-        tab_f = [torch.zeros((CHUNK, F_COLS), dtype=torch.float64, device=dev) for _ in range(2)]
-        host_i = [torch.zeros((CHUNK, I_COLS), dtype=torch.int64).pin_memory() for _ in range(2)]
-        host_f = [torch.zeros((CHUNK, F_COLS), dtype=torch.float64).pin_memory() for _ in range(2)]
+        icols, fcols = I_COLS + (2 if tc else 0), F_COLS + (6 if tc else 0)
+        tab_i = [torch.zeros((CHUNK, icols), dtype=torch.int64, device=dev) for _ in range(2)]
+        tab_f = [torch.zeros((CHUNK, fcols), dtype=torch.float64, device=dev) for _ in range(2)]
+        host_i = [torch.zeros((CHUNK, icols), dtype=torch.int64).pin_memory() for _ in range(2)]
+        host_f = [torch.zeros((CHUNK, fcols), dtype=torch.float64).pin_memory() for _ in range(2)]
         pending = []                               # (slot, first frame, rows, event) of chunks copied but not yet read
         records, cut_flags = [], []
         tot = {"psnr": 0.0, "ssim": 0.0, "lpips": 0.0, "psnr_hm": 0.0, "ssim_hm": 0.0, "lpips_hm": 0.0}
         sse_tot, ssim_p_tot = [0, 0, 0], [0.0, 0.0, 0.0]
+        # temporal: valid pixels, the three sums of the output and of the ground truth, sum of (MABD - MABD_gt)^2, all over the pairs
+        tc_tot = {"n": 0, "out": [0.0, 0.0, 0.0], "gt": [0.0, 0.0, 0.0], "mabd_sq": 0.0}
 
         def lp_sum(row, c):
             return (((row[c] + row[c + 1]) + row[c + 2]) + row[c + 3]) + row[c + 4]
@@ -256,6 +297,19 @@ def main_y4m(args):
                                      sse[2], sp[0], sp[1], sp[2])
                     else:
                         rec.update(SSE=None, SSIM_Y=None, SSIM_U=None, SSIM_V=None)
+                    if args.tc:
+                        rec["TC"] = None           # the first frame of a sequence has no partner
+                        if tc is not None and tc_flags[first + k]:
+                            nv, o3, g3 = ri[k][I_TC], rf[k][F_TC:F_TC + 3], rf[k][F_TC + 3:F_TC + 6]
+                            tc_tot["n"] += nv
+                            for q in range(3):
+                                tc_tot["out"][q] += o3[q]
+                                tc_tot["gt"][q] += g3[q]
+                            tc_tot["mabd_sq"] += (o3[2] / (3 * tc.h * tc.w) - g3[2] / (3 * tc.h * tc.w)) ** 2
+                            rec["TC"] = {"N": nv, "out": o3, "gt": g3}
+                            logging.info("NUM: %d, TC valid: %d, E_warp: %.6f (gt %.6f), MABD: %.6f (gt %.6f)", n, nv,
+                                         o3[0] / (3 * nv) if nv else float("nan"), g3[0] / (3 * nv) if nv else float("nan"),
+                                         o3[2] / (3 * tc.h * tc.w), g3[2] / (3 * tc.h * tc.w))
                     records.append(rec)
 
         def flush(slot, first, rows):
@@ -322,6 +376,10 @@ def main_y4m(args):
                     ops.yuv_sse(step.yuv[1], gt.payload, out_fmt, out=ri[I_SSE:I_SSE + 3])
                     for p in range(3):
                         ops.ssim_plane(step.yuv[1], gt.payload, out_fmt, p, out=rf[F_SSIM_P + p:F_SSIM_P + p + 1])
+                if tc is not None:
+                    if is_cut:                     # frame 0 and every scene cut: a pair never spans two sequences
+                        tc.reset()
+                    tc_flags.append(tc.push(output, gt_t, ri[I_TC:I_TC + 2], rf[F_TC:F_TC + 6]))
                 t3 = clock()
                 if writer is not None:
                     writer.submit(step.yuv[0])
@@ -369,6 +427,21 @@ def main_y4m(args):
               "Total_LPIPS_HM": tot["lpips_hm"] / n if lp_on and hm_on else None, "images": frames, "planes": planes}
     if det is not None:
         result["cuts"] = cuts
+    if args.tc:
+        result["temporal"] = None
+        if tc is not None:
+            pairs, px = sum(tc_flags), tc.h * tc.w
+            te = {"scale": args.tc_scale, "size": [tc.w, tc.h], "pairs": pairs, "raft": "file" if args.tc_raft_weights else "checkpoint",
+                  "valid_share": tc_tot["n"] / (pairs * px) if pairs else None}
+            for sfx, s3 in (("", tc_tot["out"]), ("_gt", tc_tot["gt"])):
+                te["E_warp" + sfx] = s3[0] / (3 * tc_tot["n"]) if tc_tot["n"] else None
+                te["E_static" + sfx] = s3[1] / (3 * pairs * px) if pairs else None
+                te["MABD" + sfx] = s3[2] / (3 * pairs * px) if pairs else None
+            te["MABD_mse"] = tc_tot["mabd_sq"] / pairs if pairs else None
+            result["temporal"] = te
+            logging.info("temporal (scale %d, %d pairs): %s", args.tc_scale, pairs,
+                         ", ".join("%s: %s" % (k, "null" if te[k] is None else "%.6g" % te[k]) for k in
+                                   ("valid_share", "E_warp", "E_warp_gt", "E_static", "E_static_gt", "MABD", "MABD_gt", "MABD_mse")))
     with open(os.path.join(args.save, "Metrics.json"), "w") as fh:
         json.dump(result, fh)
     if args.y4m_frames_json:
@@ -382,7 +455,8 @@ def main_y4m(args):
         with open(args.timing_json, "w") as fh:
             json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), graph=args.graph, y4m=1,
                            hist_match=int(hm_on), lpips=int(lp_on), planes=int(planes_on),
-                           scene_wait_ms=1e3 * det.wait / frames if det is not None else None), fh)
+                           scene_wait_ms=1e3 * det.wait / frames if det is not None else None,
+                           **({"tc": int(tc is not None), "tc_scale": args.tc_scale} if args.tc else {})), fh)
     logging.info("Total frame number: %d", frames)
 
 

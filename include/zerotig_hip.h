@@ -402,6 +402,27 @@ int zt_yuv_sse(const void* a, const void* b, int H, int W, int ss, int depth, un
 int zt_ssim_plane(const void* a, const void* b, int H, int W, int depth, double* partial, int npartial, double* out,
                   zt_stream_t stream);
 
+/* ---- temporal consistency of a video (zt_temporal.hip): evals.py --tc 1, zero-tig_amd/temporal.py, DESIGN 8i -------------------------
+ * zt_warp_error_f32: one pass over a frame pair.  cur, prev: planar [3][H][W]; fb, ff: planar [2][Hf][Wf], the backward flow
+ *   (cur -> prev) and the forward flow (prev -> cur) in pixels, the flow of pixel (y, x) at [(y + oy) * Wf + (x + ox)] (RAFT's
+ *   centred padding: oy = (Hf - H) / 2, ox = (Wf - W) / 2).  Per pixel, in IEEE fp32 with one rounding per operation (no fused
+ *   multiply-add), (u, v) = fb at the pixel:
+ *     px = (float)x + u, py = (float)y + v; inside = 0 <= px <= W - 1 && 0 <= py <= H - 1 (false for NaN); outside: px = py = 0
+ *     x0 = floor(px), ax = px - x0, x1 = min(x0 + 1, W - 1), the same in y
+ *     bil(p) = (1 - ay) * ((1 - ax) * p[y0][x0] + ax * p[y0][x1]) + ay * ((1 - ax) * p[y1][x0] + ax * p[y1][x1])
+ *     fu, fv = bil(ff) (through the same offset); su = u + fu, sv = v + fv
+ *     valid = inside && su * su + sv * sv <= 0.01f * ((u * u + v * v) + (fu * fu + fv * fv)) + 0.5f
+ *     d_c = cur_c - bil(prev_c), e = (d_0^2 + d_1^2) + d_2^2;  s_c = cur_c - prev_c, e0 = (s_0^2 + s_1^2) + s_2^2
+ *     b = | ((cur_0 + cur_1) + cur_2) - ((prev_0 + prev_1) + prev_2) |
+ *   out_n[0] = number of valid pixels (exact); out3 = { sum over valid pixels of e, sum over all pixels of e0, sum over all pixels
+ *   of b }, each term converted to double before it is added.  ws: 32 * nblk bytes of workspace (8-byte aligned), 1 <= nblk <= 4096
+ *   workgroups share the 256 x 4 pixel tiles; one workgroup then adds the per-block partials in index order.  No atomics: the same
+ *   input with the same nblk gives the same bits.  16-byte loads of the coalesced part where W % 4 == 0 and the pointers are
+ *   16-byte aligned (the flows also need Wf % 4 == 0 and ox % 4 == 0), value-wide loads otherwise, same result.
+ *   H, W < 1, oy, ox < 0, Hf < H + oy, Wf < W + ox, Hf * Wf >= 2^31, nblk outside 1..4096, a NULL or misaligned pointer: ZT_EINVAL. */
+int zt_warp_error_f32(const float* cur, const float* prev, const float* fb, const float* ff, int H, int W, int Hf, int Wf, int oy,
+                      int ox, void* ws, int nblk, long long* out_n, double* out3, zt_stream_t stream);
+
 /* ---- result PNGs encoded on the device (zt_png.hip) ------------------------------------------------------------------
  * predict.py:57-61, 101-104 (and evals.py's --save_images files): `Image.fromarray(u8).save(path, "PNG")`.  src: uint8 [H][W][3] (what
  * zt_quantize_u8_hwc writes) -> out: a complete zlib stream (78 01, deflate blocks, big-endian Adler-32) of the Paeth-filtered

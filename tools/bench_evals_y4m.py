@@ -10,7 +10,11 @@
       evals          evals.py   --graph 1 --precision bf16 --y4m_in LOW --y4m_gt GT --hist_match 0 (PSNR, SSIM, the plane metrics)
       evals_hm       the same with histogram matching on (PSNR_HM, SSIM_HM)
       evals_lpips    the same as `evals` with --lpips_weights (synthetic VGG weights, seeded) --lpips_precision bf16
+      evals_tc3      the same as `evals` with --tc 1 --tc_scale 3 (temporal consistency at 360 x 640)
+      evals_tc1      the same with --tc_scale 1 (at 1080 x 1920)
     frames per second and the host-side split per frame from each script's --timing_json.
+(c) the temporal kernel: HIP-event median over --reps calls of `Ops.warp_error` at 360 x 640 and 1080 x 1920, next to `Ops.warp2`
+    (the same gather pattern) and to one RAFT run of `TemporalConsistency` at the same sizes.
 
 This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
 ends the run.  Writes the JSON to --out and prints it as one line.
@@ -95,6 +99,61 @@ def kernels_mode(a):
         json.dump(out, fh)
 
 
+# ---- child: the temporal kernel alone, next to zt_warp2_f32 and to the RAFT runs that feed it -----------------------------
+def temporal_mode(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("zero-tig_amd.lib").get_lib()               # raises without a HIP device
+    ops = importlib.import_module("zero-tig_amd.ops").Ops(lib)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    temporal = importlib.import_module("zero-tig_amd.temporal")
+    dev = torch.device("cuda", 0)
+    weights = {k: torch.from_numpy(np.array(v)).to(dev) for k, v in synth.make_state(3).items() if k.startswith("raft.")}
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return statistics.median(ms), min(ms), max(ms)
+    out = {"what": "HIP-event median of %d calls: Ops.warp_error (one frame pair, flows at the frame's size), Ops.warp2 (two 3-channel "
+                   "images, flow at the frame's size) and one RAFT run of TemporalConsistency (bf16, 12 iterations); bytes = every "
+                   "array read or written once" % a.reps}
+    for h, w in ((360, 640), (1080, 1920)):
+        def frame(fn, t):
+            return torch.from_numpy(np.ascontiguousarray(np.asarray(fn(t, h, w), dtype=np.float32).reshape(1, 3, h, w))).to(dev)
+        cur, prev = frame(synth.lowlight_frame, 4), frame(synth.lowlight_frame, 3)
+        gcur, gprev = frame(synth.clean_frame, 4), frame(synth.clean_frame, 3)
+        tc = temporal.TemporalConsistency(ops, weights, dev, h, w, 1, "bf16")
+        g1, g0 = gcur * 255.0, gprev * 255.0
+        fb, ff = tc.flow(g1, g0), tc.flow(g0, g1)
+        on, o3 = torch.empty(1, dtype=torch.int64, device=dev), torch.empty(3, dtype=torch.float64, device=dev)
+        row = {}
+        for name, fn, nbytes in (("warp_error", lambda: ops.warp_error(cur, prev, fb, ff, out_n=on, out3=o3), 40 * h * w),
+                                 ("warp2", lambda: ops.warp2(fb, prev, gprev), 56 * h * w),
+                                 ("raft_flow", lambda: tc.flow(g1, g0), None)):
+            med, lo, hi = timed(fn)
+            row[name] = {"ms": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4)}
+            if nbytes is not None:
+                row[name].update(bytes=nbytes, gbs=round(nbytes / med / 1e6, 1))
+            print("[bench_evals_y4m] %dx%d %s %s" % (h, w, name, row[name]), file=sys.stderr, flush=True)
+        row["valid_share"] = int(on.item()) / (h * w)
+        row["sums"] = o3.tolist()
+        out["%dx%d" % (h, w)] = row
+        del tc, fb, ff
+        torch.cuda.empty_cache()
+    with open(a.json, "w") as fh:
+        json.dump(out, fh)
+
+
 # ---- driver ---------------------------------------------------------------------------------------------------------------------
 def _one_pair(t):
     import numpy as np
@@ -153,38 +212,49 @@ def gpu_step(cmd, limit, env=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels"])
+    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels", "temporal"])
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--distinct", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--settings", type=str, nargs="*", default=["predict", "evals", "evals_hm", "evals_lpips"],
-                    choices=["predict", "evals", "evals_hm", "evals_lpips"])
+    ap.add_argument("--settings", type=str, nargs="*", default=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1"],
+                    choices=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1"])
     ap.add_argument("--skip-kernels", action="store_true", help="part (b) only")
+    ap.add_argument("--skip-temporal", action="store_true", help="without the temporal kernel's own timing (part (c))")
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "evals_y4m_1080p.json"))
     a = ap.parse_args()
     if a.mode == "kernels":
         return kernels_mode(a)
+    if a.mode == "temporal":
+        return temporal_mode(a)
     out = {"what": "evals.py --y4m_in / --y4m_gt next to predict.py --y4m_in, --graph 1 --precision bf16, over one synthetic 1080p "
                    "C420mpeg2 pair of %d frames (%d distinct), %d runs per setting, the runs alternating, one session on one box; fps "
                    "and the host-side split per frame from each script's --timing_json (predict: first frame read to last stream "
                    "closed, two Y4M streams written; evals: first frame read to the last metric read back, nothing written); "
                    "evals = --hist_match 0, no LPIPS; evals_hm = histogram matching on; evals_lpips = --hist_match 0 with a seeded "
                    "synthetic VGG state dict, --lpips_precision bf16; kernels = Ops.yuv_sse / Ops.ssim_plane alone, HIP-event median "
-                   "of %d calls" % (a.frames, a.distinct, a.repeats, a.reps), "cpus": len(os.sched_getaffinity(0))}
+                   "of %d calls; evals_tc3 / evals_tc1 = evals with --tc 1 at --tc_scale 3 / 1; temporal_kernels = Ops.warp_error, "
+                   "Ops.warp2 and one RAFT run of TemporalConsistency alone" % (a.frames, a.distinct, a.repeats, a.reps),
+            "cpus": len(os.sched_getaffinity(0))}
     tmp = tempfile.mkdtemp(prefix="zt_bench_evals_y4m_")
     try:
         if not a.skip_kernels:
             kj = os.path.join(tmp, "kernels.json")
             gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "kernels", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
             out["kernels"] = json.load(open(kj))
+        if not a.skip_temporal:
+            kj = os.path.join(tmp, "temporal.json")
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "temporal", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
+            out["temporal_kernels"] = json.load(open(kj))
         files = make_pair(tmp, a.frames, a.distinct)
         env = dict(os.environ, PYTHONPATH=ROOT)
         common = ["--model_pretrain", files["weights"], "--graph", "1", "--precision", "bf16", "--y4m_in", files["low"]]
         extra = {"predict": [], "evals": ["--y4m_gt", files["gt"], "--hist_match", "0"], "evals_hm": ["--y4m_gt", files["gt"]],
-                 "evals_lpips": ["--y4m_gt", files["gt"], "--hist_match", "0", "--lpips_weights", files["lpips"], "--lpips_precision", "bf16"]}
+                 "evals_lpips": ["--y4m_gt", files["gt"], "--hist_match", "0", "--lpips_weights", files["lpips"], "--lpips_precision", "bf16"],
+                 "evals_tc3": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "3"],
+                 "evals_tc1": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "1"]}
         loops, wall = {s: [] for s in a.settings}, {s: [] for s in a.settings}
         for rep in range(a.repeats):
             for s in a.settings:

@@ -474,6 +474,36 @@ class Ops:
                       self._s(pa))
         return out
 
+    # ---- temporal consistency of a frame pair (zt_temporal.hip) -------------------------------------------
+    def warp_error(self, cur, prev, fb, ff, out_n=None, out3=None):
+        """cur, prev [1,3,H,W]; fb, ff [1,2,Hf,Wf]: the backward (cur -> prev) and forward (prev -> cur) flow in pixels at RAFT's
+        padded size (the frame centred: oy = (Hf - H) // 2, ox = (Wf - W) // 2) -> (int64 [1], float64 [3]) on the device: the
+        number of pixels that pass the forward-backward test, the sum over them of the squared error against the warped previous
+        frame, and over all pixels the sums of the squared frame difference and of the absolute brightness difference.
+        Nothing synchronises; `out_n` / `out3` (e.g. cells of a table row) are overwritten."""
+        _f32c(cur), _f32c(prev), _f32c(fb), _f32c(ff)
+        assert cur.dim() == 4 and cur.shape[0] == 1 and cur.shape[1] == 3 and cur.shape == prev.shape, (cur.shape, prev.shape)
+        assert fb.dim() == 4 and fb.shape[0] == 1 and fb.shape[1] == 2 and fb.shape == ff.shape, (fb.shape, ff.shape)
+        H, W = int(cur.shape[2]), int(cur.shape[3])
+        Hf, Wf = int(fb.shape[2]), int(fb.shape[3])
+        assert Hf >= H and Wf >= W and all(t.device == cur.device for t in (prev, fb, ff)), (H, W, Hf, Wf)
+        dev = cur.device
+        # one 256 x 4 tile per workgroup up to 4096 tiles (1024 workgroups striding over the tiles measured the same, DESIGN 8i)
+        nblk = max(1, min(4096, -(-H // 4) * -(-W // 256)))
+        ws = self.__dict__.setdefault("_warp_error_workspaces", {})
+        key = (nblk, str(dev))
+        if key not in ws:
+            ws[key] = torch.empty(4 * nblk, dtype=torch.int64, device=dev)
+        if out_n is None:
+            out_n = torch.empty(1, dtype=torch.int64, device=dev)
+        if out3 is None:
+            out3 = torch.empty(3, dtype=torch.float64, device=dev)
+        assert out_n.numel() == 1 and out_n.dtype == torch.int64 and out_n.is_contiguous() and out_n.device == dev
+        assert tuple(out3.shape) == (3,) and out3.dtype == torch.float64 and out3.is_contiguous() and out3.device == dev
+        self.lib.call("zt_warp_error_f32", cur, prev, fb, ff, H, W, Hf, Wf, (Hf - H) // 2, (Wf - W) // 2, ws[key], nblk, out_n, out3,
+                      self._s(cur))
+        return out_n, out3
+
     # ---- evals.py's frame metrics, results left on the device (the video loop reads a table back every 64 frames) -------
     def sqdiff_u8(self, a, b, out=None):
         """the integer of `psnr_u8`: sum (round(a*255) - round(b*255))^2 -> int64 [1] on the device, no read-back"""
