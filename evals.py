@@ -32,7 +32,8 @@ parser.add_argument("--of_scale", type=int, default=3)
 parser.add_argument("--dataset", type=str, default="RLV")
 parser.add_argument("--gain", type=int, default=100, help="kept for CLI compatibility (unused upstream as well)")
 parser.add_argument("--save_images", type=int, default=None, help="write the first N result pairs (evals.py:162); default 20")
-parser.add_argument("--hist_match", type=int, default=1, help="0: skip histogram matching and the *_HM metrics (evals.py:114)")
+parser.add_argument("--hist_match", type=int, default=None,
+                    help="0: skip histogram matching and the *_HM metrics (evals.py:114); default 1 (with --noref 1 there is nothing to match)")
 parser.add_argument("--lpips_weights", type=str, default=None,
                     help="torch.save(lpips.LPIPS(net='vgg').state_dict(), FILE); default: no LPIPS (fields null)")
 parser.add_argument("--lpips_precision", type=str, default="fp32", choices=["fp32", "bf16"])
@@ -72,6 +73,12 @@ parser.add_argument("--tc", type=int, default=0, choices=[0, 1],
                     help="1: temporal consistency (DESIGN 8i): per frame pair of a sequence the warping error (Lai et al. 2018, occlusion "
                          "test of Ruder et al. 2016), the plain frame difference and MABD (Jiang and Zheng 2019) of the denoise result, "
                          "next to the same numbers of the ground truth; flows from RAFT on the ground-truth frames; needs --y4m_in")
+parser.add_argument("--noref", type=int, default=0, choices=[0, 1],
+                    help="1: grade --y4m_in without ground truth (DESIGN 8j): per frame the lightness order error of the denoise result "
+                         "against the decoded input (LOE at full resolution, LOE_50 on the 50-pixel grid of the papers' tables), the mean "
+                         "lightness of both and its gain, the entropies of the two lightness histograms and the saturated / black shares "
+                         "of the result, under \"noref\" in Metrics.json; takes no --y4m_gt; with --tc 1 the flows come from RAFT on the "
+                         "denoise result itself; needs --y4m_in")
 parser.add_argument("--tc_scale", type=int, default=None,
                     help="integer S >= 1: the temporal metrics are taken at (H // S, W // S); default --of_scale; needs --tc 1")
 parser.add_argument("--tc_raft_weights", type=str, default=None,
@@ -86,10 +93,25 @@ CHUNK = 64                                         # frames per read-back of the
 I_SSE, I_SQ, I_SQ_HM, I_COLS = 0, 3, 4, 5
 F_SSIM, F_SSIM_HM, F_SSIM_P, F_LP, F_LP_HM, F_COLS = 0, 1, 2, 5, 10, 15
 I_TC, F_TC = I_COLS, F_COLS                        # --tc 1: two more integers and six more doubles behind them
+NR_I, NR_F = 12, 4                                 # --noref 1: behind those, Ops.noref of the full grid and of the LOE_50 grid
+NR_KEYS = ("LOE", "LOE_50", "L_in", "L_out", "gain", "entropy_in", "entropy_out", "sat_out", "black_out")
 
 
 def check_y4m_args(args):
     """every argument check of the video mode, before anything touches the device -> True when the video mode was asked for"""
+    explicit_hm = args.hist_match is not None
+    if not explicit_hm:
+        args.hist_match = 0 if args.noref else 1
+    if args.noref:
+        if args.y4m_in is None:
+            parser.error("--noref 1 needs --y4m_in: it grades a raw video against its own input")
+        if args.y4m_gt is not None:
+            parser.error("--noref 1 grades without ground truth: --y4m_gt cannot be combined with it")
+        if args.lpips_weights is not None:
+            parser.error("--noref 1 grades without ground truth: --lpips_weights cannot be combined with it (LPIPS needs --y4m_gt)")
+        if explicit_hm and args.hist_match:
+            parser.error("--noref 1 grades without ground truth: --hist_match %d cannot be combined with it (there is no histogram "
+                         "to match)" % args.hist_match)
     if not args.tc:
         for flag in ("tc_scale", "tc_raft_weights"):
             if getattr(args, flag) is not None:
@@ -105,7 +127,7 @@ def check_y4m_args(args):
         if args.y4m_scene_cut != 0:
             parser.error("--y4m_scene_cut needs --y4m_in")
         return False
-    if args.y4m_gt is None:
+    if args.y4m_gt is None and not args.noref:
         parser.error("--y4m_in needs --y4m_gt: the ground-truth stream the frames are graded against")
     if args.y4m_gt == "-":
         parser.error("--y4m_gt must be a file: only --y4m_in can be read from standard input")
@@ -126,7 +148,7 @@ def check_y4m_args(args):
         parser.error("--y4m_scene_cut is a threshold in [0, 1], 0 = off; got %g" % args.y4m_scene_cut)
     if args.y4m_cuts_json is not None and not args.y4m_scene_cut > 0:
         parser.error("--y4m_cuts_json needs --y4m_scene_cut T (T > 0) and --y4m_in")
-    if not os.path.isfile(args.y4m_gt):
+    if not args.noref and not os.path.isfile(args.y4m_gt):
         parser.error("--y4m_gt %s: no such file" % args.y4m_gt)
     if args.tc:
         if args.tc_scale is None:
@@ -161,14 +183,31 @@ class GroundTruth:
         return self.ops.yuv_to_planar_f32_sized(self.payload, self.fmt, self.size, out=self.rgb, bufs=self._bufs)
 
 
+def loe50_grid(H, W):
+    """the sample grid of LOE_50: the short side becomes 50, the other side keeps the aspect, each rounded half up"""
+    m = min(H, W)
+    return (100 * H + m) // (2 * m), (100 * W + m) // (2 * m)
+
+
+def noref_values(full, ents, sub):
+    """the per-frame numbers of --noref 1 from what `Ops.noref` returns on the full grid (six integers `full`, two entropies
+    `ents`) and on the LOE_50 grid (`sub`): [Ns, S_loe, S_a, S_b, n_sat, n_black]"""
+    ns = full[0]
+    l_in, l_out = full[2] / ns, full[3] / ns
+    return {"LOE": full[1] / (ns * (ns - 1)) if ns > 1 else None, "LOE_50": sub[1] / sub[0], "L_in": l_in, "L_out": l_out,
+            "gain": l_out / l_in if full[2] else None, "entropy_in": ents[0], "entropy_out": ents[1], "sat_out": full[4] / ns,
+            "black_out": full[5] / ns}
+
+
 def _psnr_of(sq, n):
     return float("inf") if sq == 0 else 10.0 * math.log10(255.0 ** 2 * n / sq)
 
 
 def main_y4m(args):
     """--y4m_in LOW --y4m_gt GT: the low stream through InferStep(yuv=) as in predict.py, every frame graded against the ground
-    truth's.  Each metric kernel writes into a row of a table on the device; the table is read back every CHUNK frames (and at the
-    end), one chunk late, so the host keeps running ahead of the device."""
+    truth's; --y4m_in LOW --noref 1: the same loop without a ground-truth reader, every frame graded against its own decoded
+    input.  Each metric kernel writes into a row of a table on the device; the table is read back every CHUNK frames
+    (and at the end), one chunk late, so the host keeps running ahead of the device."""
     import importlib
     y4m = importlib.import_module("zero-tig_amd.y4m")
     os.makedirs(args.save, exist_ok=True)
@@ -177,17 +216,19 @@ def main_y4m(args):
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", args.gpu)
+    noref = bool(args.noref)
     reader = y4m.Y4MReader(args.y4m_in)
     try:
-        gt_reader = y4m.Y4MReader(args.y4m_gt)
+        gt_reader = None if noref else y4m.Y4MReader(args.y4m_gt)
     except BaseException:
         reader.close()
         raise
     writer = None
     try:
-        head, gt_head = reader.header, gt_reader.header
+        head = reader.header
+        gt_head = head if noref else gt_reader.header
         fmt, gt_fmt = head.format(args.y4m_matrix), gt_head.format(args.y4m_matrix)
-        for name, h, f in (("input", head, fmt), ("ground truth", gt_head, gt_fmt)):
+        for name, h, f in (("input", head, fmt),) + (() if noref else (("ground truth", gt_head, gt_fmt),)):
             logging.info("Y4M %s: %dx%d C%s %d-bit %s %s", name, h.W, h.H, h.ctag, f.depth, "full" if h.full else "limited", args.y4m_matrix)
         out_depth = args.y4m_out_depth or fmt.depth
         W, H = args.y4m_size or (fmt.W, fmt.H)
@@ -202,15 +243,17 @@ def main_y4m(args):
                                                                        yuv_out_depth=out_depth, yuv_size=args.y4m_size)
         ops = utils._ops()
         out_fmt = step.yuv_format
-        gt = GroundTruth(ops, gt_fmt, (W, H), dev)
+        gt = None if noref else GroundTruth(ops, gt_fmt, (W, H), dev)
         planes_on, why = True, None
-        if (gt_fmt.W, gt_fmt.H, gt_fmt.ss, gt_fmt.depth) != (out_fmt.W, out_fmt.H, out_fmt.ss, out_fmt.depth):
+        if noref:                                  # no ground-truth payload to hold the planes against
+            planes_on = False
+        elif (gt_fmt.W, gt_fmt.H, gt_fmt.ss, gt_fmt.depth) != (out_fmt.W, out_fmt.H, out_fmt.ss, out_fmt.depth):
             planes_on = False
             why = "the denoise payload is %dx%d %d %d-bit, the ground truth %dx%d %d %d-bit" % (
                 out_fmt.W, out_fmt.H, out_fmt.ss, out_fmt.depth, gt_fmt.W, gt_fmt.H, gt_fmt.ss, gt_fmt.depth)
         elif min(out_fmt.chroma_shape) < 7 or min(out_fmt.H, out_fmt.W) < 7:
             planes_on, why = False, "a plane is smaller than the 7 x 7 window of SSIM"
-        if not planes_on:
+        if not planes_on and not noref:
             logging.info("plane metrics off (planes: null): %s", why)
         tc, tc_flags = None, []
         if args.tc:
@@ -235,7 +278,11 @@ def main_y4m(args):
         npix = 3 * H * W
 
         # the table: two device slots and two pinned host slots, used in turn
-        icols, fcols = I_COLS + (2 if tc else 0), F_COLS + (6 if tc else 0)
+        i_nr, f_nr = I_COLS + (2 if tc else 0), F_COLS + (6 if tc else 0)
+        icols, fcols = i_nr + (NR_I if noref else 0), f_nr + (NR_F if noref else 0)
+        grid50 = loe50_grid(H, W)
+        # no-reference: per key the sum of the frames' values and the number of frames that have one; sum of S_a and of S_b
+        nr_tot, nr_n, nr_s = dict.fromkeys(NR_KEYS, 0.0), dict.fromkeys(NR_KEYS, 0), [0, 0]
         tab_i = [torch.zeros((CHUNK, icols), dtype=torch.int64, device=dev) for _ in range(2)]
         tab_f = [torch.zeros((CHUNK, fcols), dtype=torch.float64, device=dev) for _ in range(2)]
         host_i = [torch.zeros((CHUNK, icols), dtype=torch.int64).pin_memory() for _ in range(2)]
@@ -250,6 +297,33 @@ def main_y4m(args):
         def lp_sum(row, c):
             return (((row[c] + row[c + 1]) + row[c + 2]) + row[c + 3]) + row[c + 4]
 
+        def grade_noref(n, rec, ri, rf):
+            """frame n of --noref 1 from its row of the table: the record, the totals and the log lines"""
+            full, sub = ri[i_nr:i_nr + 6], ri[i_nr + 6:i_nr + 12]
+            v = noref_values(full, rf[f_nr:f_nr + 2], sub)
+            for key in NR_KEYS:
+                if v[key] is not None:
+                    nr_tot[key] += v[key]
+                    nr_n[key] += 1
+            nr_s[0] += full[2]
+            nr_s[1] += full[3]
+            rec["noref"] = dict(v, ints=full, ints_50=sub)
+            logging.info("NUM: %d, " + ", ".join(key + ": %s" for key in NR_KEYS), n,
+                         *["null" if v[key] is None else "%.4f" % v[key] for key in NR_KEYS])
+            logging.info("Total LOE: %s, Total LOE_50: %.4f, Total L_out: %.4f, Total gain: %s",
+                         "%.4f" % (nr_tot["LOE"] / nr_n["LOE"]) if nr_n["LOE"] else "null", nr_tot["LOE_50"] / n, nr_tot["L_out"] / n,
+                         "%.4f" % (nr_s[1] / nr_s[0]) if nr_s[0] else "null")
+            if args.tc:
+                rec["TC"] = None                   # the first frame of a sequence has no partner
+                if tc is not None and tc_flags[n - 1]:
+                    nv, o3 = ri[I_TC], rf[F_TC:F_TC + 3]
+                    tc_tot["n"] += nv
+                    for q in range(3):
+                        tc_tot["out"][q] += o3[q]
+                    rec["TC"] = {"N": nv, "out": o3, "gt": None}
+                    logging.info("NUM: %d, TC valid: %d, E_warp: %.6f, MABD: %.6f (flows from the output)", n, nv,
+                                 o3[0] / (3 * nv) if nv else float("nan"), o3[2] / (3 * tc.h * tc.w))
+
         def drain(keep):
             """read every pending chunk but the newest `keep`: totals, records and the log lines"""
             while len(pending) > keep:
@@ -259,6 +333,10 @@ def main_y4m(args):
                 for k in range(rows):
                     n = first + k + 1
                     rec = {"frame": first + k, "cut": bool(cut_flags[first + k])}
+                    if noref:
+                        grade_noref(n, rec, ri[k], rf[k])
+                        records.append(rec)
+                        continue
                     psnr, ssim = _psnr_of(ri[k][I_SQ], npix), rf[k][F_SSIM]
                     tot["psnr"] += psnr
                     tot["ssim"] += ssim
@@ -331,7 +409,7 @@ def main_y4m(args):
                 except StopIteration:
                     payload = None
                 try:
-                    gt_payload = next(gt_reader)
+                    gt_payload = payload if noref else next(gt_reader)
                     gt_frames += 1
                 except StopIteration:
                     gt_payload = None
@@ -357,12 +435,17 @@ def main_y4m(args):
                 enhance, output, illum = step(payload, is_cut)
                 reader.release(step.loaded)
                 t2 = clock()
-                gt_t = gt.load(gt_payload)
-                gt_reader.release(gt.loaded)
                 slot, row = (frames // CHUNK) & 1, frames % CHUNK
                 ri, rf = tab_i[slot][row], tab_f[slot][row]
-                ops.sqdiff_u8(output, gt_t, out=ri[I_SQ:I_SQ + 1])
-                ops.ssim_u8_dev(output, gt_t, out=rf[F_SSIM:F_SSIM + 1])
+                if noref:                          # step.x: the decoded input after any resize, what the network saw
+                    ops.noref(step.x, output, out_i=ri[i_nr:i_nr + 6], out_f=rf[f_nr:f_nr + 2])
+                    ops.noref(step.x, output, grid=grid50, out_i=ri[i_nr + 6:i_nr + 12], out_f=rf[f_nr + 2:f_nr + 4])
+                    gt_t = output                  # --tc 1: the flows come from the enhanced stream itself
+                else:
+                    gt_t = gt.load(gt_payload)
+                    gt_reader.release(gt.loaded)
+                    ops.sqdiff_u8(output, gt_t, out=ri[I_SQ:I_SQ + 1])
+                    ops.ssim_u8_dev(output, gt_t, out=rf[F_SSIM:F_SSIM + 1])
                 if lp_on:
                     gt_feat = lpips_model.features(gt_t)
                     lpips_model.distance_dev(lpips_model.features(output), gt_feat, rf[F_LP:F_LP + 5])
@@ -408,7 +491,8 @@ def main_y4m(args):
             except BaseException as e:             # noqa: BLE001
                 errors.append(e)
         reader.close()
-        gt_reader.close()
+        if gt_reader is not None:
+            gt_reader.close()
         if errors and sys.exc_info()[0] is None:
             raise errors[0]
     n = max(frames, 1)
@@ -425,6 +509,13 @@ def main_y4m(args):
     result = {"Total_PSNR": tot["psnr"] / n, "Total_SSIM": tot["ssim"] / n, "Total_LPIPS": tot["lpips"] / n if lp_on else None,
               "Total_PSNR_HM": tot["psnr_hm"] / n if hm_on else None, "Total_SSIM_HM": tot["ssim_hm"] / n if hm_on else None,
               "Total_LPIPS_HM": tot["lpips_hm"] / n if lp_on and hm_on else None, "images": frames, "planes": planes}
+    if noref:
+        for k in ("Total_PSNR", "Total_SSIM"):
+            result[k] = None
+        result["noref"] = dict({"graded": "denoise"}, **{k: nr_tot[k] / nr_n[k] if nr_n[k] else None for k in NR_KEYS})
+        result["noref"]["gain"] = nr_s[1] / nr_s[0] if nr_s[0] else None       # of the stream: sum S_b / sum S_a
+        logging.info("no-reference (%d frames, the denoise result against the decoded input): %s", frames,
+                     ", ".join("%s: %s" % (k, "null" if result["noref"][k] is None else "%.6g" % result["noref"][k]) for k in NR_KEYS))
     if det is not None:
         result["cuts"] = cuts
     if args.tc:
@@ -438,6 +529,8 @@ def main_y4m(args):
                 te["E_static" + sfx] = s3[1] / (3 * pairs * px) if pairs else None
                 te["MABD" + sfx] = s3[2] / (3 * pairs * px) if pairs else None
             te["MABD_mse"] = tc_tot["mabd_sq"] / pairs if pairs else None
+            if noref:                              # the output was pushed in the ground truth's place: those numbers repeat the output's
+                te.update(E_warp_gt=None, E_static_gt=None, MABD_gt=None, MABD_mse=None, flow_from="output")
             result["temporal"] = te
             logging.info("temporal (scale %d, %d pairs): %s", args.tc_scale, pairs,
                          ", ".join("%s: %s" % (k, "null" if te[k] is None else "%.6g" % te[k]) for k in
@@ -454,7 +547,7 @@ def main_y4m(args):
         per = {k + "_ms": 1e3 * v / frames for k, v in t.items()}
         with open(args.timing_json, "w") as fh:
             json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), graph=args.graph, y4m=1,
-                           hist_match=int(hm_on), lpips=int(lp_on), planes=int(planes_on),
+                           hist_match=int(hm_on), lpips=int(lp_on), planes=int(planes_on), **({"noref": 1} if noref else {}),
                            scene_wait_ms=1e3 * det.wait / frames if det is not None else None,
                            **({"tc": int(tc is not None), "tc_scale": args.tc_scale} if args.tc else {})), fh)
     logging.info("Total frame number: %d", frames)

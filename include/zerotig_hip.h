@@ -423,6 +423,24 @@ int zt_ssim_plane(const void* a, const void* b, int H, int W, int depth, double*
 int zt_warp_error_f32(const float* cur, const float* prev, const float* fb, const float* ff, int H, int W, int Hf, int Wf, int oy,
                       int ox, void* ws, int nblk, long long* out_n, double* out3, zt_stream_t stream);
 
+/* ---- no-reference grading of a video (zt_noref.hip): evals.py --noref 1, DESIGN 8j --------------------------------------------------
+ * a, b: planar fp32 [3][H][W], the decoded input and the enhanced frame.  Level = zt_quant_u8(v, 1) = rint(v * 255) & 255 (one fp32
+ * multiply), lightness L = max of the three levels; La from a, Lb from b.  Sample (i, j) of the Hs x Ws grid is the pixel at row
+ * ((2i + 1) H) / (2 Hs), column ((2j + 1) W) / (2 Ws) in integers: (Hs, Ws) = (H, W) is every pixel once, a larger grid repeats pixels.
+ * zt_lightness_joint_hist_f32: hist[x * 256 + y] = number of samples with (La, Lb) = (x, y), uint32 [256][256]; hist is zeroed in
+ *   stream order first.  Each workgroup counts at most 65532 samples in a private table of 16-bit counters in LDS (128 KB) and adds
+ *   its non-zero counters to hist with integer atomics: any order of the additions gives the same table.  16-byte loads on the full
+ *   grid when W % 4 == 0 and both frames are 16-byte aligned, value-wide loads otherwise, same result.  H, W outside 1..2^20,
+ *   Hs, Ws < 1, Hs * Ws >= 2^32, a NULL or misaligned pointer: ZT_EINVAL.
+ * zt_noref_from_hist: with C the 2-D inclusive cumulative sum of hist, R[x] = C[x][255], K[y] = C[255][y], ha / hb the marginals:
+ *   out_i = { Ns = C[255][255], S_loe = sum hist[x][y] (R[x] + K[y] - 2 C[x][y]), S_a = sum x ha[x], S_b = sum y hb[y], hb[255],
+ *   hb[0] } as exact 64-bit integers (S_loe < Ns^2: exact for Ns up to 2^31), out_f = { E_a, E_b }, the entropies in bits of the two
+ *   marginals, -sum p log2 p with p = h / Ns in fp64, added in level order.  R[x] + K[y] - 2 C[x][y] is the number of samples q for
+ *   which (La_p >= La_q) xor (Lb_p >= Lb_q) for a sample p at (x, y), so S_loe is the lightness order error summed over all ordered
+ *   pairs.  hist: 16-byte aligned, read only; one workgroup, no workspace.  Deterministic; nothing synchronises. */
+int zt_lightness_joint_hist_f32(const float* a, const float* b, int H, int W, int Hs, int Ws, unsigned int* hist, zt_stream_t stream);
+int zt_noref_from_hist(const unsigned int* hist, long long* out_i /* [6] */, double* out_f /* [2] */, zt_stream_t stream);
+
 /* ---- result PNGs encoded on the device (zt_png.hip) ------------------------------------------------------------------
  * predict.py:57-61, 101-104 (and evals.py's --save_images files): `Image.fromarray(u8).save(path, "PNG")`.  src: uint8 [H][W][3] (what
  * zt_quantize_u8_hwc writes) -> out: a complete zlib stream (78 01, deflate blocks, big-endian Adler-32) of the Paeth-filtered

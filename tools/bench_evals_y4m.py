@@ -16,6 +16,12 @@
 (c) the temporal kernel: HIP-event median over --reps calls of `Ops.warp_error` at 360 x 640 and 1080 x 1920, next to `Ops.warp2`
     (the same gather pattern) and to one RAFT run of `TemporalConsistency` at the same sizes.
 
+(d) no reference: `evals_noref` = evals.py --y4m_in LOW --noref 1 in part (b), and the two entry points of zt_noref.hip
+    alone at 1080p -- the joint histogram on the full grid, `zt_noref_from_hist`, `Ops.noref` on the full and on the LOE_50 grid --
+    next to `Ops.ssim_u8_dev` in the same process, on four inputs: the synthetic low-light frame against its clean twin, 13 dark
+    levels against noise, one bin (two constant frames) and uniform noise.  `--settings evals_noref --skip-kernels --skip-temporal
+    --out profiles/noref_1080p.json` is the run behind that file.
+
 This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
 ends the run.  Writes the JSON to --out and prints it as one line.
 Usage: python tools/bench_evals_y4m.py [--frames 256] [--out profiles/evals_y4m_1080p.json]"""
@@ -154,6 +160,60 @@ def temporal_mode(a):
         json.dump(out, fh)
 
 
+# ---- child: the two entry points of zt_noref.hip alone, next to zt_ssim_u8_f32 ----------------------------------------------
+def noref_mode(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("zero-tig_amd.lib").get_lib()               # raises without a HIP device
+    ops = importlib.import_module("zero-tig_amd.ops").Ops(lib)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+
+    def dev_frame(x):
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(1, 3, H, W))).to(dev)
+
+    def timed(fn):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return {"ms": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
+    inputs = {"synth_lowlight": (dev_frame(synth.lowlight_frame(3, H, W)), dev_frame(synth.clean_frame(3, H, W))),
+              "dark_13_levels": (dev_frame(rng.integers(0, 13, (3, H, W)) / np.float32(255)), dev_frame(rng.random((3, H, W), dtype=np.float32))),
+              "one_bin": (torch.full((1, 3, H, W), 0.02, device=dev), torch.full((1, 3, H, W), 0.5, device=dev)),
+              "uniform_noise": (dev_frame(rng.random((3, H, W), dtype=np.float32)), dev_frame(rng.random((3, H, W), dtype=np.float32)))}
+    grid50 = (50, 89)
+    out = {"what": "HIP-event median of %d calls at 1080 x 1920: hist = zt_lightness_joint_hist_f32 on the full grid (the memset of the "
+                   "table included; it reads both frames once, bytes = 24 H W), from_hist = zt_noref_from_hist, noref / noref_50 = "
+                   "Ops.noref (both kernels) on the full grid / on the 50 x 89 grid, ssim_u8 = Ops.ssim_u8_dev on the same frames" % a.reps}
+    for name, (x, y) in inputs.items():
+        hist = torch.empty((256, 256), dtype=torch.uint32, device=dev)
+        oi, of = torch.empty(6, dtype=torch.int64, device=dev), torch.empty(2, dtype=torch.float64, device=dev)
+        one = torch.empty(1, dtype=torch.float64, device=dev)
+        row = {"hist": timed(lambda: ops.lightness_joint_hist(x, y, out=hist))}
+        row["hist"].update(bytes=24 * H * W, gbs=round(24 * H * W / row["hist"]["ms"] / 1e6, 1))
+        row["from_hist"] = timed(lambda: lib.call("zt_noref_from_hist", hist, oi, of, ops._s(x)))
+        row["noref"] = timed(lambda: ops.noref(x, y, out_i=oi, out_f=of))
+        row["noref_50"] = timed(lambda: ops.noref(x, y, grid=grid50, out_i=oi, out_f=of))
+        row["ssim_u8"] = timed(lambda: ops.ssim_u8_dev(x, y, out=one))
+        ops.noref(x, y, out_i=oi, out_f=of)
+        h = hist.cpu().numpy()
+        row.update(occupied_bins=int((h != 0).sum()), occupied_La_levels=int((h.sum(axis=1) != 0).sum()), ints=oi.tolist(), entropies=of.tolist())
+        out[name] = row
+        print("[bench_evals_y4m] noref %s %s" % (name, row), file=sys.stderr, flush=True)
+    with open(a.json, "w") as fh:
+        json.dump(out, fh)
+
+
 # ---- driver ---------------------------------------------------------------------------------------------------------------------
 def _one_pair(t):
     import numpy as np
@@ -212,14 +272,14 @@ def gpu_step(cmd, limit, env=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels", "temporal"])
+    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels", "temporal", "noref"])
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--distinct", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--settings", type=str, nargs="*", default=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1"],
-                    choices=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1"])
+                    choices=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1", "evals_noref"])
     ap.add_argument("--skip-kernels", action="store_true", help="part (b) only")
     ap.add_argument("--skip-temporal", action="store_true", help="without the temporal kernel's own timing (part (c))")
     ap.add_argument("--step-timeout", type=int, default=240)
@@ -229,6 +289,8 @@ def main():
         return kernels_mode(a)
     if a.mode == "temporal":
         return temporal_mode(a)
+    if a.mode == "noref":
+        return noref_mode(a)
     out = {"what": "evals.py --y4m_in / --y4m_gt next to predict.py --y4m_in, --graph 1 --precision bf16, over one synthetic 1080p "
                    "C420mpeg2 pair of %d frames (%d distinct), %d runs per setting, the runs alternating, one session on one box; fps "
                    "and the host-side split per frame from each script's --timing_json (predict: first frame read to last stream "
@@ -236,7 +298,8 @@ def main():
                    "evals = --hist_match 0, no LPIPS; evals_hm = histogram matching on; evals_lpips = --hist_match 0 with a seeded "
                    "synthetic VGG state dict, --lpips_precision bf16; kernels = Ops.yuv_sse / Ops.ssim_plane alone, HIP-event median "
                    "of %d calls; evals_tc3 / evals_tc1 = evals with --tc 1 at --tc_scale 3 / 1; temporal_kernels = Ops.warp_error, "
-                   "Ops.warp2 and one RAFT run of TemporalConsistency alone" % (a.frames, a.distinct, a.repeats, a.reps),
+                   "Ops.warp2 and one RAFT run of TemporalConsistency alone; evals_noref = --noref 1, no ground truth (DESIGN 8j); "
+                   "noref_kernels = the two entry points of zt_noref.hip alone" % (a.frames, a.distinct, a.repeats, a.reps),
             "cpus": len(os.sched_getaffinity(0))}
     tmp = tempfile.mkdtemp(prefix="zt_bench_evals_y4m_")
     try:
@@ -248,13 +311,18 @@ def main():
             kj = os.path.join(tmp, "temporal.json")
             gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "temporal", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
             out["temporal_kernels"] = json.load(open(kj))
+        if "evals_noref" in a.settings:
+            kj = os.path.join(tmp, "noref.json")
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "noref", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
+            out["noref_kernels"] = json.load(open(kj))
         files = make_pair(tmp, a.frames, a.distinct)
         env = dict(os.environ, PYTHONPATH=ROOT)
         common = ["--model_pretrain", files["weights"], "--graph", "1", "--precision", "bf16", "--y4m_in", files["low"]]
         extra = {"predict": [], "evals": ["--y4m_gt", files["gt"], "--hist_match", "0"], "evals_hm": ["--y4m_gt", files["gt"]],
                  "evals_lpips": ["--y4m_gt", files["gt"], "--hist_match", "0", "--lpips_weights", files["lpips"], "--lpips_precision", "bf16"],
                  "evals_tc3": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "3"],
-                 "evals_tc1": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "1"]}
+                 "evals_tc1": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "1"],
+                 "evals_noref": ["--noref", "1"]}
         loops, wall = {s: [] for s in a.settings}, {s: [] for s in a.settings}
         for rep in range(a.repeats):
             for s in a.settings:

@@ -537,6 +537,49 @@ class Ops:
         self.lib.call("zt_ssim_u8_f32", a, b, H, W, ws[key], npart, out, self._s(a))
         return out
 
+    # ---- no-reference grading of a frame against its own input (zt_noref.hip) ----------------------------
+    def _noref_args(self, a, b, grid):
+        _f32c(a), _f32c(b)
+        assert a.dim() == 4 and a.shape[0] == 1 and a.shape[1] == 3 and a.shape == b.shape, (tuple(a.shape), tuple(b.shape))
+        assert a.device == b.device, (a.device, b.device)
+        H, W = int(a.shape[2]), int(a.shape[3])
+        assert H >= 1 and W >= 1, (H, W)
+        assert grid is None or (len(grid) == 2 and all(int(v) == v for v in grid)), grid
+        Hs, Ws = (H, W) if grid is None else (int(grid[0]), int(grid[1]))
+        assert Hs >= 1 and Ws >= 1 and Hs * Ws < 1 << 32, (Hs, Ws)
+        return H, W, Hs, Ws
+
+    def lightness_joint_hist(self, a, b, grid=None, out=None):
+        """a (the decoded input), b (the enhanced frame): fp32 [1,3,H,W] -> uint32 [256,256] on the device: the number of samples
+        of the `grid` = (Hs, Ws) (default: every pixel once; sample (i, j) is the pixel at row ((2i+1) H) // (2 Hs), column
+        ((2j+1) W) // (2 Ws)) whose 8-bit lightness max(R, G, B) is x in `a` and y in `b`, at [x, y].  Nothing synchronises."""
+        H, W, Hs, Ws = self._noref_args(a, b, grid)
+        if out is None:
+            out = torch.empty((256, 256), dtype=torch.uint32, device=a.device)
+        assert tuple(out.shape) == (256, 256) and out.dtype == torch.uint32 and out.is_contiguous() and out.device == a.device
+        self.lib.call("zt_lightness_joint_hist_f32", a, b, H, W, Hs, Ws, out, self._s(a))
+        return out
+
+    def noref(self, a, b, grid=None, out_i=None, out_f=None):
+        """the no-reference numbers of frame `b` against its input `a` on `grid` (see `lightness_joint_hist`) -> (int64 [6],
+        float64 [2]) on the device: {Ns, S_loe, S_a, S_b, n_sat, n_black} and the entropies in bits of the two lightness
+        marginals (include/zerotig_hip.h).  Nothing synchronises; `out_i` / `out_f` (e.g. cells of a table row) are overwritten.
+        The 256 KB histogram between the two kernels is cached per device."""
+        self._noref_args(a, b, grid)
+        dev = a.device
+        ws = self.__dict__.setdefault("_noref_workspaces", {})
+        if str(dev) not in ws:
+            ws[str(dev)] = torch.empty((256, 256), dtype=torch.uint32, device=dev)
+        if out_i is None:
+            out_i = torch.empty(6, dtype=torch.int64, device=dev)
+        if out_f is None:
+            out_f = torch.empty(2, dtype=torch.float64, device=dev)
+        assert tuple(out_i.shape) == (6,) and out_i.dtype == torch.int64 and out_i.is_contiguous() and out_i.device == dev
+        assert tuple(out_f.shape) == (2,) and out_f.dtype == torch.float64 and out_f.is_contiguous() and out_f.device == dev
+        hist = self.lightness_joint_hist(a, b, grid, out=ws[str(dev)])
+        self.lib.call("zt_noref_from_hist", hist, out_i, out_f, self._s(a))
+        return out_i, out_f
+
     def psnr_u8(self, a, b):
         """evals.py:83-85: cv2.PSNR of round(a*255), round(b*255) -> python float (inf when identical); one 8-byte read-back."""
         _f32c(a), _f32c(b)
