@@ -87,6 +87,19 @@ parser.add_argument("--tc_raft_weights", type=str, default=None,
                          "in the reference, RAFT is never trained there and is built after the weights file is read, so unless your "
                          "checkpoint was made to hold a trained RAFT these are freshly drawn weights (seeded by --seed) and the warping "
                          "error measures little; needs --tc 1")
+parser.add_argument("--tc_viz", type=str, default=None,
+                    help="PATH.y4m: one diagnostic picture per frame (DESIGN 8k), 2w x 2h at the reduced size of --tc_scale, 8-bit C420 "
+                         "limited range: the colour wheel of the backward and of the forward flow, the denoise result with the pixels "
+                         "that leave the frame in magenta and those that fail the forward-backward test in cyan, and the warping "
+                         "error of the valid pixels in grey; the first frame of a sequence has white flow panels; needs --tc 1")
+parser.add_argument("--tc_viz_max", type=float, default=None,
+                    help="0 (default): each pair's flows are drawn at the scale of their joint largest radius; R > 0: R pixels of the "
+                         "reduced frame are full saturation in every picture, longer flows are drawn at 0.75 brightness; needs --tc_viz")
+parser.add_argument("--tc_viz_gain", type=float, default=None,
+                    help="the grey of the error panel is min(1, sqrt(e / 3) * G); default 4; needs --tc_viz")
+parser.add_argument("--tc_flo_dir", type=str, default=None,
+                    help="per graded pair write DIR/%%06d_bwd.flo (current -> previous) and DIR/%%06d_fwd.flo (previous -> current), "
+                         "Middlebury .flo files at the reduced size, in reduced-frame pixels, numbered by the current frame; needs --tc 1")
 
 CHUNK = 64                                         # frames per read-back of the metric table
 # columns of the metric table's two halves: int64 (exact sums) and float64
@@ -113,9 +126,13 @@ def check_y4m_args(args):
             parser.error("--noref 1 grades without ground truth: --hist_match %d cannot be combined with it (there is no histogram "
                          "to match)" % args.hist_match)
     if not args.tc:
-        for flag in ("tc_scale", "tc_raft_weights"):
+        for flag in ("tc_scale", "tc_raft_weights", "tc_viz", "tc_viz_max", "tc_viz_gain", "tc_flo_dir"):
             if getattr(args, flag) is not None:
                 parser.error("--%s needs --tc 1" % flag)
+    if args.tc_viz is None:
+        for flag in ("tc_viz_max", "tc_viz_gain"):
+            if getattr(args, flag) is not None:
+                parser.error("--%s needs --tc_viz" % flag)
     if args.y4m_in is None:
         if args.tc:
             parser.error("--tc 1 needs --y4m_in")
@@ -157,6 +174,19 @@ def check_y4m_args(args):
             parser.error("--tc_scale is an integer >= 1; got %d" % args.tc_scale)
         if args.tc_raft_weights is not None and not os.path.isfile(args.tc_raft_weights):
             parser.error("--tc_raft_weights %s: no such file" % args.tc_raft_weights)
+        if args.tc_viz is not None:
+            args.tc_viz_max = 0.0 if args.tc_viz_max is None else args.tc_viz_max
+            args.tc_viz_gain = 4.0 if args.tc_viz_gain is None else args.tc_viz_gain
+            if not (0 <= args.tc_viz_max < math.inf):
+                parser.error("--tc_viz_max is a flow length in pixels >= 0, 0 = each pair at its own scale; got %g" % args.tc_viz_max)
+            if not (0 <= args.tc_viz_gain < math.inf):
+                parser.error("--tc_viz_gain is a factor >= 0; got %g" % args.tc_viz_gain)
+            if args.tc_viz == "-":
+                parser.error("--tc_viz must be a file: standard output carries the log")
+            for flag in ("y4m_in", "y4m_gt", "y4m_out"):
+                other = getattr(args, flag)
+                if other not in (None, "-") and os.path.abspath(other) == os.path.abspath(args.tc_viz):
+                    parser.error("--tc_viz %s is the file of --%s" % (args.tc_viz, flag))
     return True
 
 
@@ -223,7 +253,7 @@ def main_y4m(args):
     except BaseException:
         reader.close()
         raise
-    writer = None
+    writer, viz_writer, flo_writer = None, None, None
     try:
         head = reader.header
         gt_head = head if noref else gt_reader.header
@@ -256,17 +286,32 @@ def main_y4m(args):
         if not planes_on and not noref:
             logging.info("plane metrics off (planes: null): %s", why)
         tc, tc_flags = None, []
+        viz_on, flo_on = False, False
         if args.tc:
             temporal = importlib.import_module("zero-tig_amd.temporal")
             why = temporal.too_small(H, W, args.tc_scale)
             if why is not None:
                 logging.info("temporal metrics off (temporal: null): %s", why)
+                if args.tc_viz is not None or args.tc_flo_dir is not None:
+                    logging.info("temporal pictures off as well: %s are not written", " and ".join(
+                        n for n, v in (("--tc_viz " + str(args.tc_viz), args.tc_viz), ("the .flo files of --tc_flo_dir", args.tc_flo_dir))
+                        if v is not None))
             else:
+                viz_on, flo_on = args.tc_viz is not None, args.tc_flo_dir is not None
                 if args.tc_raft_weights is not None:
                     raft_w = temporal.load_raft_weights(args.tc_raft_weights, model.raft.state_dict(), dev)
                 else:
                     raft_w = {"raft." + k: v.data for k, v in model.raft.state_dict().items()}
-                tc = temporal.TemporalConsistency(ops, raft_w, dev, H, W, args.tc_scale, model.precision)
+                tc = temporal.TemporalConsistency(ops, raft_w, dev, H, W, args.tc_scale, model.precision, keep_pair=viz_on)
+        if viz_on:                                 # the picture: rendered in float, encoded by the kernel of the enhance stream
+            viz_head = head.resized(2 * tc.w, 2 * tc.h)._replace(ctag="420mpeg2", color_range="LIMITED")
+            viz_fmt = viz_head.format(args.y4m_matrix)
+            viz_rgb = torch.empty((1, 3, 2 * tc.h, 2 * tc.w), dtype=torch.float32, device=dev)
+            viz_yuv = torch.empty(viz_fmt.frame_bytes, dtype=torch.uint8, device=dev)
+            viz_writer = y4m.Y4MWriter(args.tc_viz, viz_head)
+        if flo_on:
+            os.makedirs(args.tc_flo_dir, exist_ok=True)
+            flo_writer = importlib.import_module("zero-tig_amd.flowio").FloWriter()
         det, cuts, scores, rels = None, [], [], []
         if args.y4m_scene_cut > 0:
             det = importlib.import_module("zero-tig_amd.scenecut").SceneCut(ops, dev, fmt, args.y4m_scene_cut)
@@ -399,7 +444,7 @@ def main_y4m(args):
 
         frames, gt_frames = 0, 0
         clock = time.perf_counter
-        t = {"decode_wait": 0.0, "step": 0.0, "metrics": 0.0, "readback": 0.0, "write": 0.0}
+        t = {"decode_wait": 0.0, "step": 0.0, "metrics": 0.0, "readback": 0.0, "write": 0.0, "viz": 0.0}
         t_first = None
         with torch.no_grad():
             while True:
@@ -463,6 +508,13 @@ def main_y4m(args):
                     if is_cut:                     # frame 0 and every scene cut: a pair never spans two sequences
                         tc.reset()
                     tc_flags.append(tc.push(output, gt_t, ri[I_TC:I_TC + 2], rf[F_TC:F_TC + 6]))
+                t_m = clock()
+                if viz_on:                         # one picture per frame, of the pair or of the frame alone
+                    tc.viz(viz_rgb, "out", args.tc_viz_max, args.tc_viz_gain)
+                    viz_writer.submit(ops.rgb_f32_to_yuv(viz_rgb, viz_fmt, out=viz_yuv))
+                if flo_on and tc_flags[-1]:
+                    for flow, name in ((tc.fb, "bwd"), (tc.ff, "fwd")):
+                        flo_writer.submit(os.path.join(args.tc_flo_dir, "%06d_%s.flo" % (frames, name)), ops.flow_pack(flow, tc.h, tc.w))
                 t3 = clock()
                 if writer is not None:
                     writer.submit(step.yuv[0])
@@ -474,7 +526,8 @@ def main_y4m(args):
                 t5 = clock()
                 t["decode_wait"] += t1 - t0
                 t["step"] += t2 - t1
-                t["metrics"] += t3 - t2
+                t["metrics"] += t_m - t2
+                t["viz"] += t3 - t_m
                 t["write"] += t4 - t3
                 t["readback"] += t5 - t4
             t5 = clock()
@@ -485,11 +538,12 @@ def main_y4m(args):
             t["readback"] += t_end - t5
     finally:
         errors = []
-        if writer is not None:
-            try:
-                writer.close()
-            except BaseException as e:             # noqa: BLE001
-                errors.append(e)
+        for w in (writer, viz_writer, flo_writer):
+            if w is not None:
+                try:
+                    w.close()
+                except BaseException as e:         # noqa: BLE001
+                    errors.append(e)
         reader.close()
         if gt_reader is not None:
             gt_reader.close()
@@ -531,6 +585,10 @@ def main_y4m(args):
             te["MABD_mse"] = tc_tot["mabd_sq"] / pairs if pairs else None
             if noref:                              # the output was pushed in the ground truth's place: those numbers repeat the output's
                 te.update(E_warp_gt=None, E_static_gt=None, MABD_gt=None, MABD_mse=None, flow_from="output")
+            if viz_on:
+                te["viz"] = {"path": args.tc_viz, "size": [2 * tc.w, 2 * tc.h], "max": args.tc_viz_max, "gain": args.tc_viz_gain}
+            if flo_on:
+                te["flo_dir"] = args.tc_flo_dir
             result["temporal"] = te
             logging.info("temporal (scale %d, %d pairs): %s", args.tc_scale, pairs,
                          ", ".join("%s: %s" % (k, "null" if te[k] is None else "%.6g" % te[k]) for k in
@@ -544,7 +602,10 @@ def main_y4m(args):
         with open(args.y4m_cuts_json, "w") as fh:
             json.dump({"threshold": args.y4m_scene_cut, "cuts": cuts, "score": scores, "rel": rels}, fh)
     if args.timing_json and frames:
-        per = {k + "_ms": 1e3 * v / frames for k, v in t.items()}
+        per = {k + "_ms": 1e3 * v / frames for k, v in t.items() if k != "viz"}
+        if viz_on or flo_on:                       # the time `submit` waited for a free slot is part of viz_ms
+            per["viz"] = {"viz_ms": 1e3 * t["viz"] / frames,
+                          "wait_writer_ms": 1e3 * sum(w.wait_writer for w in (viz_writer, flo_writer) if w is not None) / frames}
         with open(args.timing_json, "w") as fh:
             json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), graph=args.graph, y4m=1,
                            hist_match=int(hm_on), lpips=int(lp_on), planes=int(planes_on), **({"noref": 1} if noref else {}),

@@ -423,6 +423,39 @@ int zt_ssim_plane(const void* a, const void* b, int H, int W, int depth, double*
 int zt_warp_error_f32(const float* cur, const float* prev, const float* fb, const float* ff, int H, int W, int Hf, int Wf, int oy,
                       int ox, void* ws, int nblk, long long* out_n, double* out3, zt_stream_t stream);
 
+/* ---- looking at the flows of --tc 1 (zt_flowviz.hip): evals.py --tc_viz / --tc_flo_dir, utils/flow_viz.py, DESIGN 8k ------------------
+ * Flows: planar [2][Hf][Wf] fp32, the window (oy, ox, H, W) as in zt_warp_error_f32.  IEEE fp32, one rounding per operation, no fused
+ * multiply-add, no library transcendental (sqrtf and / are correctly rounded): a numpy float32 restatement gives the same bits.
+ * zt_flow_radmax_f32: out1[0] = the largest sqrtf(u * u + v * v) over the window of fa and, when not NULL, fb, over the pixels whose
+ *   u * u + v * v is finite (so both components are finite, and the result always is); 0 when there is none.  ws: 4 * nblk bytes,
+ *   1 <= nblk <= 4096.  A maximum does not depend on the order: no atomics, same input, same bits.
+ * zt_flow_to_rgb: the colour wheel of Baker et al. 2007 at the scale R = rad_dev[0] (a float on the device):
+ *     den = R + 1e-5f; un = u / den, vn = v / den; r2 = un * un + vn * vn; rad = sqrtf(r2); r2 not finite (NaN included): black
+ *     a = atan2(-vn, -un) by a fixed sequence of fp32 operations (zt_flowviz.hip; the sign of a zero counts)
+ *     fk = (a / pi + 1) * 27 (pi in float32, so that +-pi give exactly 0 and 54); k0 = min(max((int)floorf(fk), 0), 54); f = fk - floorf(fk); k1 = k0 + 1, 55 -> 0
+ *     col = (1 - f) * (wheel[k0] / 255) + f * (wheel[k1] / 255); rad <= 1: col = 1 - rad * (1 - col), otherwise col = col * 0.75f
+ *     level = (int)floorf(255 * col) clamped to 0..255
+ *   out_u8: uint8 [H][W][3] (NULL: not written); out_f32: planar fp32 [3][H][W] of level / 255.f (NULL: not written); at least one.
+ *   bgr = 1: the channels in the order blue, green, red.
+ * zt_flow_wheel: pure host query, the 55 x 3 levels of the wheel.
+ * zt_tc_viz_f32: out = planar fp32 [3][2H][2W], one picture of four panels of the frame pair of zt_warp_error_f32, whose per-pixel
+ *   u, v, inside, ax, ay, fu, fv, valid, e it computes with the same operations: top left / top right the wheel colour of fb / ff at
+ *   the pixel (both at rad_dev[0]); bottom left cur where valid, (1, 0, 1) where the pixel lands outside the frame, (0, 1, 1) where it
+ *   fails the forward-backward test; bottom right min(1, sqrtf(e / 3) * gain) where valid, 0 elsewhere.  prev = NULL (no partner;
+ *   fb, ff, rad_dev are not read and may be NULL): white, white, cur, black.  gain: finite, >= 0.
+ * zt_flow_pack_hwc_f32: the window as interleaved [H][W][2], the payload of a Middlebury .flo file.
+ * 16-byte loads / stores where W % 4 == 0 and the pointer is 16-byte aligned (flows: also Wf % 4 == 0 and ox % 4 == 0; the uint8
+ * output: 32-bit stores, 4-byte aligned), value by value otherwise, same result.  H, W < 1, oy, ox < 0, Hf < H + oy, Wf < W + ox,
+ * Hf * Wf >= 2^31, H > 262140, a NULL or misaligned pointer: ZT_EINVAL. */
+int zt_flow_radmax_f32(const float* fa, const float* fb /* or NULL */, int H, int W, int Hf, int Wf, int oy, int ox, float* ws,
+                       int nblk, float* out1, zt_stream_t stream);
+int zt_flow_to_rgb(const float* flow, int H, int W, int Hf, int Wf, int oy, int ox, const float* rad_dev, unsigned char* out_u8,
+                   float* out_f32, int bgr, zt_stream_t stream);
+int zt_flow_wheel(unsigned char* out165);
+int zt_tc_viz_f32(const float* cur, const float* prev /* or NULL */, const float* fb, const float* ff, int H, int W, int Hf, int Wf,
+                  int oy, int ox, const float* rad_dev, float gain, float* out, zt_stream_t stream);
+int zt_flow_pack_hwc_f32(const float* flow, int H, int W, int Hf, int Wf, int oy, int ox, float* out, zt_stream_t stream);
+
 /* ---- no-reference grading of a video (zt_noref.hip): evals.py --noref 1, DESIGN 8j --------------------------------------------------
  * a, b: planar fp32 [3][H][W], the decoded input and the enhanced frame.  Level = zt_quant_u8(v, 1) = rint(v * 255) & 255 (one fp32
  * multiply), lightness L = max of the three levels; La from a, Lb from b.  Sample (i, j) of the Hs x Ws grid is the pixel at row

@@ -22,6 +22,13 @@
     levels against noise, one bin (two constant frames) and uniform noise.  `--settings evals_noref --skip-kernels --skip-temporal
     --out profiles/noref_1080p.json` is the run behind that file.
 
+(e) the pictures of --tc 1: `evals_tcviz` = `evals_tc3` with --tc_viz and --tc_flo_dir (a 1280 x 720 stream and two
+    .flo files per pair written), `evals_tcviz_pic` = with --tc_viz alone; the yardstick is `evals_tc3` in the same run
+    (`tcviz_over_tc3_ms_per_frame`).  With either, the kernels of zt_flowviz.hip alone at 360 x 640: `Ops.tc_viz` with the bytes it
+    moves, `Ops.flow_radmax` of two flows, `Ops.flow_pack`, and `Ops.rgb_f32_to_yuv` of the picture.  `--settings evals_tc3
+    evals_tcviz_pic evals_tcviz --skip-kernels --skip-temporal --frames 128 --out profiles/evals_tcviz_1080p.json` is the run behind
+    that file.
+
 This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
 ends the run.  Writes the JSON to --out and prints it as one line.
 Usage: python tools/bench_evals_y4m.py [--frames 256] [--out profiles/evals_y4m_1080p.json]"""
@@ -214,6 +221,62 @@ def noref_mode(a):
         json.dump(out, fh)
 
 
+# ---- child: the kernels of zt_flowviz.hip alone at the reduced size of --tc_scale 3 --------------------------------------
+def tcviz_mode(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("zero-tig_amd.lib").get_lib()               # raises without a HIP device
+    ops = importlib.import_module("zero-tig_amd.ops").Ops(lib)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    temporal = importlib.import_module("zero-tig_amd.temporal")
+    y4m = importlib.import_module("zero-tig_amd.y4m")
+    dev = torch.device("cuda", 0)
+    weights = {k: torch.from_numpy(np.array(v)).to(dev) for k, v in synth.make_state(3).items() if k.startswith("raft.")}
+    h, w = H // 3, W // 3
+
+    def timed(fn):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return {"ms": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
+
+    def frame(fn, t):
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(fn(t, h, w), dtype=np.float32).reshape(1, 3, h, w))).to(dev)
+    cur, prev = frame(synth.lowlight_frame, 4), frame(synth.lowlight_frame, 3)
+    tc = temporal.TemporalConsistency(ops, weights, dev, h, w, 1, "bf16")
+    g1, g0 = frame(synth.clean_frame, 4) * 255.0, frame(synth.clean_frame, 3) * 255.0
+    fb, ff = tc.flow(g1, g0), tc.flow(g0, g1)
+    rad = ops.flow_radmax(fb, ff, h=h, w=w)
+    pic = torch.empty((1, 3, 2 * h, 2 * w), dtype=torch.float32, device=dev)
+    packed = torch.empty((h, w, 2), dtype=torch.float32, device=dev)
+    fmt = y4m.YuvFormat(2 * w, 2 * h, 420, 1, "bt709", 0)
+    yuv = torch.empty(fmt.frame_bytes, dtype=torch.uint8, device=dev)
+    out = {"what": "HIP-event median of %d calls at %d x %d (flows padded to %d x %d): tc_viz = zt_tc_viz_f32 of a pair (bytes: the two "
+                   "frames, the two flows and the picture once each, 88 a pixel; the 20 gathered taps come on top), tc_viz_alone = "
+                   "the same without a partner, radmax = zt_flow_radmax_f32 of both flows, pack = zt_flow_pack_hwc_f32, encode = "
+                   "Ops.rgb_f32_to_yuv of the %d x %d picture" % (a.reps, h, w, fb.shape[2], fb.shape[3], 2 * h, 2 * w),
+           "radius": rad.item()}
+    for name, fn, nbytes in (("tc_viz", lambda: ops.tc_viz(cur, prev, fb, ff, rad, 4.0, out=pic), 88 * h * w),
+                             ("tc_viz_alone", lambda: ops.tc_viz(cur, None, None, None, None, 4.0, out=pic), 60 * h * w),
+                             ("radmax", lambda: ops.flow_radmax(fb, ff, h=h, w=w, out=rad), 16 * h * w),
+                             ("pack", lambda: ops.flow_pack(fb, h, w, out=packed), 16 * h * w),
+                             ("encode", lambda: ops.rgb_f32_to_yuv(pic, fmt, out=yuv), 48 * h * w + fmt.frame_bytes)):
+        out[name] = dict(timed(fn), bytes=nbytes)
+        out[name]["gbs"] = round(nbytes / out[name]["ms"] / 1e6, 1)
+        print("[bench_evals_y4m] tcviz %s %s" % (name, out[name]), file=sys.stderr, flush=True)
+    with open(a.json, "w") as fh:
+        json.dump(out, fh)
+
+
 # ---- driver ---------------------------------------------------------------------------------------------------------------------
 def _one_pair(t):
     import numpy as np
@@ -272,14 +335,15 @@ def gpu_step(cmd, limit, env=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels", "temporal", "noref"])
+    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels", "temporal", "noref", "tcviz"])
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--distinct", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--settings", type=str, nargs="*", default=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1"],
-                    choices=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1", "evals_noref"])
+                    choices=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1", "evals_noref", "evals_tcviz_pic",
+                             "evals_tcviz"])
     ap.add_argument("--skip-kernels", action="store_true", help="part (b) only")
     ap.add_argument("--skip-temporal", action="store_true", help="without the temporal kernel's own timing (part (c))")
     ap.add_argument("--step-timeout", type=int, default=240)
@@ -291,6 +355,8 @@ def main():
         return temporal_mode(a)
     if a.mode == "noref":
         return noref_mode(a)
+    if a.mode == "tcviz":
+        return tcviz_mode(a)
     out = {"what": "evals.py --y4m_in / --y4m_gt next to predict.py --y4m_in, --graph 1 --precision bf16, over one synthetic 1080p "
                    "C420mpeg2 pair of %d frames (%d distinct), %d runs per setting, the runs alternating, one session on one box; fps "
                    "and the host-side split per frame from each script's --timing_json (predict: first frame read to last stream "
@@ -299,7 +365,8 @@ def main():
                    "synthetic VGG state dict, --lpips_precision bf16; kernels = Ops.yuv_sse / Ops.ssim_plane alone, HIP-event median "
                    "of %d calls; evals_tc3 / evals_tc1 = evals with --tc 1 at --tc_scale 3 / 1; temporal_kernels = Ops.warp_error, "
                    "Ops.warp2 and one RAFT run of TemporalConsistency alone; evals_noref = --noref 1, no ground truth (DESIGN 8j); "
-                   "noref_kernels = the two entry points of zt_noref.hip alone" % (a.frames, a.distinct, a.repeats, a.reps),
+                   "noref_kernels = the two entry points of zt_noref.hip alone; evals_tcviz / evals_tcviz_pic = evals_tc3 with --tc_viz and "
+                   "--tc_flo_dir / with --tc_viz alone (DESIGN 8k), tcviz_kernels = the kernels of zt_flowviz.hip alone" % (a.frames, a.distinct, a.repeats, a.reps),
             "cpus": len(os.sched_getaffinity(0))}
     tmp = tempfile.mkdtemp(prefix="zt_bench_evals_y4m_")
     try:
@@ -315,7 +382,12 @@ def main():
             kj = os.path.join(tmp, "noref.json")
             gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "noref", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
             out["noref_kernels"] = json.load(open(kj))
+        if any(s.startswith("evals_tcviz") for s in a.settings):
+            kj = os.path.join(tmp, "tcviz.json")
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "tcviz", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
+            out["tcviz_kernels"] = json.load(open(kj))
         files = make_pair(tmp, a.frames, a.distinct)
+        viz, flo = os.path.join(tmp, "viz.y4m"), os.path.join(tmp, "flo")
         env = dict(os.environ, PYTHONPATH=ROOT)
         common = ["--model_pretrain", files["weights"], "--graph", "1", "--precision", "bf16", "--y4m_in", files["low"]]
         extra = {"predict": [], "evals": ["--y4m_gt", files["gt"], "--hist_match", "0"], "evals_hm": ["--y4m_gt", files["gt"]],
@@ -323,7 +395,9 @@ def main():
                  "evals_tc3": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "3"],
                  "evals_tc1": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "1"],
                  "evals_noref": ["--noref", "1"]}
-        loops, wall = {s: [] for s in a.settings}, {s: [] for s in a.settings}
+        extra["evals_tcviz_pic"] = extra["evals_tc3"] + ["--tc_viz", viz]
+        extra["evals_tcviz"] = extra["evals_tcviz_pic"] + ["--tc_flo_dir", flo]
+        loops, wall, written = {s: [] for s in a.settings}, {s: [] for s in a.settings}, {}
         for rep in range(a.repeats):
             for s in a.settings:
                 save, tj = os.path.join(tmp, "out_" + s), os.path.join(tmp, "timing_%s.json" % s)
@@ -332,7 +406,18 @@ def main():
                 loops[s].append(json.load(open(tj)))
                 if s != "predict" and rep == 0:
                     out.setdefault("metrics", {})[s] = json.load(open(os.path.join(save, "Metrics.json")))
+                    te = out["metrics"][s].get("temporal") or {}
+                    if "viz" in te:                # the temporary directory's name says nothing
+                        te["viz"]["path"] = os.path.basename(te["viz"]["path"])
+                    if "flo_dir" in te:
+                        te["flo_dir"] = os.path.basename(te["flo_dir"])
                 shutil.rmtree(save, ignore_errors=True)
+                if os.path.exists(viz):
+                    written.setdefault(s, {}).update(viz_bytes=os.path.getsize(viz))
+                    os.remove(viz)
+                if os.path.isdir(flo):
+                    written.setdefault(s, {}).update(flo_files=len(os.listdir(flo)))
+                    shutil.rmtree(flo, ignore_errors=True)
                 print("[bench_evals_y4m] %s run %d: %.1f s wall, %.2f fps" % (s, rep, wall[s][-1], loops[s][-1]["fps"]), file=sys.stderr, flush=True)
         out["end_to_end"] = {}
         for s in a.settings:
@@ -340,6 +425,13 @@ def main():
             out["end_to_end"][s] = {"fps_runs": [round(v, 2) for v in fps], "fps_median": round(statistics.median(fps), 2),
                                     "fps_spread": round(max(fps) - min(fps), 2), "ms_per_frame_median": round(1e3 / statistics.median(fps), 3),
                                     "loop": sorted(loops[s], key=lambda l: l["fps"])[len(fps) // 2], "wall_s": [round(v, 2) for v in wall[s]]}
+            if s in written:
+                out["end_to_end"][s]["written"] = written[s]
+        if "evals_tc3" in a.settings:
+            base = out["end_to_end"]["evals_tc3"]["ms_per_frame_median"]
+            for s in a.settings:
+                if s.startswith("evals_tcviz"):
+                    out["end_to_end"][s]["tcviz_over_tc3_ms_per_frame"] = round(out["end_to_end"][s]["ms_per_frame_median"] - base, 3)
         if "predict" in a.settings:
             base = out["end_to_end"]["predict"]["ms_per_frame_median"]
             for s in a.settings:

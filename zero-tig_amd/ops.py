@@ -504,6 +504,102 @@ class Ops:
                       self._s(cur))
         return out_n, out3
 
+    # ---- looking at those flows (zt_flowviz.hip) -----------------------------------------------------------
+    @staticmethod
+    def _flow_window(flow, h, w):
+        """a flow [1,2,Hf,Wf] (or [2,Hf,Wf]) and the frame's size inside it -> (H, W, Hf, Wf, oy, ox), centred as in `warp_error`"""
+        _f32c(flow)
+        assert flow.dim() in (3, 4) and tuple(flow.shape[:-2]) in ((2,), (1, 2)), tuple(flow.shape)
+        Hf, Wf = int(flow.shape[-2]), int(flow.shape[-1])
+        H, W = Hf if h is None else int(h), Wf if w is None else int(w)
+        assert 1 <= H <= Hf and 1 <= W <= Wf, (H, W, Hf, Wf)
+        return H, W, Hf, Wf, (Hf - H) // 2, (Wf - W) // 2
+
+    def _radius(self, radius, dev):
+        """a radius given as a number or as a device tensor -> float32 [1] on the device (a number is written by a fill, in
+        stream order, into a cell of its own)"""
+        if torch.is_tensor(radius):
+            assert radius.numel() == 1 and radius.dtype == torch.float32 and radius.is_contiguous() and radius.device == dev, \
+                (radius.dtype, tuple(radius.shape), radius.device)
+            return radius
+        return torch.full((1,), float(radius), dtype=torch.float32, device=dev)
+
+    def flow_wheel(self):
+        """-> uint8 [55, 3] on the host: the colour wheel the kernels use"""
+        out = torch.empty((55, 3), dtype=torch.uint8)
+        self.lib.call("zt_flow_wheel", out)
+        return out
+
+    def flow_radmax(self, fa, fb=None, h=None, w=None, out=None):
+        """the largest finite radius sqrt(u^2 + v^2) over the frame's window (h x w, centred) of one flow or of two ->
+        float32 [1] on the device.  Nothing synchronises; `out` is overwritten."""
+        H, W, Hf, Wf, oy, ox = self._flow_window(fa, h, w)
+        dev = fa.device
+        if fb is not None:
+            _f32c(fb)
+            assert fb.shape == fa.shape and fb.device == dev, (fa.shape, fb.shape)
+        nblk = max(1, min(4096, -(-H // 4) * -(-W // 256)))
+        ws = self.__dict__.setdefault("_radmax_workspaces", {})
+        key = (nblk, str(dev))
+        if key not in ws:
+            ws[key] = torch.empty(nblk, dtype=torch.float32, device=dev)
+        if out is None:
+            out = torch.empty(1, dtype=torch.float32, device=dev)
+        assert out.numel() == 1 and out.dtype == torch.float32 and out.is_contiguous() and out.device == dev
+        self.lib.call("zt_flow_radmax_f32", fa, fb, H, W, Hf, Wf, oy, ox, ws[key], nblk, out, self._s(fa))
+        return out
+
+    def flow_to_rgb(self, flow, h=None, w=None, radius=None, u8=False, bgr=False, out=None):
+        """the colour wheel of Baker et al. 2007 over the frame's window of a flow -> uint8 [h, w, 3] (u8=True, the layout of the
+        reference's `flow_to_image`) or fp32 [1, 3, h, w] of level / 255.  `radius`: the flow drawn at full saturation, a number
+        or a float32 [1] on the device; None: this flow's own largest radius (`flow_radmax`).  Nothing synchronises."""
+        H, W, Hf, Wf, oy, ox = self._flow_window(flow, h, w)
+        dev = flow.device
+        rad = self.flow_radmax(flow, h=H, w=W) if radius is None else self._radius(radius, dev)
+        if out is None:
+            out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if u8 else torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
+        assert out.dtype == (torch.uint8 if u8 else torch.float32) and out.numel() == 3 * H * W and out.is_contiguous() and \
+            out.device == dev, (out.dtype, tuple(out.shape))
+        self.lib.call("zt_flow_to_rgb", flow, H, W, Hf, Wf, oy, ox, rad, out if u8 else None, None if u8 else out, int(bool(bgr)),
+                      self._s(flow))
+        return out
+
+    def tc_viz(self, cur, prev, fb, ff, radius, gain, out=None):
+        """the four-panel picture of a frame pair -> fp32 [1, 3, 2H, 2W]: the wheel colours of the backward and of the forward flow
+        (both at `radius`, a number or a float32 [1] on the device), the current frame with the pixels that leave the frame in
+        magenta and those that fail the forward-backward test in cyan, and sqrt(e / 3) * gain of the valid pixels in grey
+        (arguments as `warp_error`).  prev=None (a frame without a partner; fb, ff, radius are ignored): white, white, cur, black.
+        Nothing synchronises."""
+        _f32c(cur)
+        assert cur.dim() == 4 and cur.shape[0] == 1 and cur.shape[1] == 3, cur.shape
+        H, W = int(cur.shape[2]), int(cur.shape[3])
+        dev = cur.device
+        if out is None:
+            out = torch.empty((1, 3, 2 * H, 2 * W), dtype=torch.float32, device=dev)
+        assert out.dtype == torch.float32 and out.numel() == 12 * H * W and out.is_contiguous() and out.device == dev, \
+            (out.dtype, tuple(out.shape))
+        if prev is None:
+            self.lib.call("zt_tc_viz_f32", cur, None, None, None, H, W, H, W, 0, 0, None, float(gain), out, self._s(cur))
+            return out
+        _f32c(prev), _f32c(fb), _f32c(ff)
+        assert prev.shape == cur.shape, (cur.shape, prev.shape)
+        assert fb.dim() == 4 and fb.shape[0] == 1 and fb.shape[1] == 2 and fb.shape == ff.shape, (fb.shape, ff.shape)
+        Hf, Wf = int(fb.shape[2]), int(fb.shape[3])
+        assert Hf >= H and Wf >= W and all(t.device == dev for t in (prev, fb, ff)), (H, W, Hf, Wf)
+        self.lib.call("zt_tc_viz_f32", cur, prev, fb, ff, H, W, Hf, Wf, (Hf - H) // 2, (Wf - W) // 2, self._radius(radius, dev),
+                      float(gain), out, self._s(cur))
+        return out
+
+    def flow_pack(self, flow, h=None, w=None, out=None):
+        """the frame's window of a planar padded flow -> fp32 [h, w, 2], u and v interleaved: the payload of a .flo file"""
+        H, W, Hf, Wf, oy, ox = self._flow_window(flow, h, w)
+        if out is None:
+            out = torch.empty((H, W, 2), dtype=torch.float32, device=flow.device)
+        assert out.dtype == torch.float32 and out.numel() == 2 * H * W and out.is_contiguous() and out.device == flow.device, \
+            (out.dtype, tuple(out.shape))
+        self.lib.call("zt_flow_pack_hwc_f32", flow, H, W, Hf, Wf, oy, ox, out, self._s(flow))
+        return out
+
     # ---- evals.py's frame metrics, results left on the device (the video loop reads a table back every 64 frames) -------
     def sqdiff_u8(self, a, b, out=None):
         """the integer of `psnr_u8`: sum (round(a*255) - round(b*255))^2 -> int64 [1] on the device, no read-back"""

@@ -61,9 +61,12 @@ class TemporalConsistency:
     next frame) before `push` returns to the caller's stream order.
     `ri`: int64 [2], `rf`: float64 [6] on the device, e.g. slices of a table row: ri[0], rf[0:3] = `Ops.warp_error` of the output
     pair, ri[1], rf[3:6] = of the ground-truth pair.  The first frame after `reset()` writes nothing.
-    `fb`, `ff`: the flows last used ([1,2,Hp,Wp], the padded size)."""
+    `fb`, `ff`: the flows last used ([1,2,Hp,Wp], the padded size).
+    `keep_pair=True` keeps the reduced frames of the last push (and of its partner), so that `viz` can draw them:
+       tc.viz(out, which="out", radius=0.0, gain=4.0)   # the four-panel picture of the last pushed frame into out [1,3,2h,2w]
+    `push` and its numbers are the same either way."""
 
-    def __init__(self, ops, raft_weights, dev, H, W, scale, precision):
+    def __init__(self, ops, raft_weights, dev, H, W, scale, precision, keep_pair=False):
         why = too_small(H, W, scale)
         if why is not None or scale < 1:
             raise ValueError("TemporalConsistency: scale %d at %dx%d: %s" % (scale, W, H, why or "the scale is an integer >= 1"))
@@ -74,6 +77,9 @@ class TemporalConsistency:
         self.plan.two_streams = False
         self.fb = self.ff = None
         self.pairs = 0
+        self.keep_pair = bool(keep_pair)
+        self._last = None                          # keep_pair: (cur, prev or None) of the last push
+        self._radius = torch.empty(1, dtype=torch.float32, device=dev) if keep_pair else None
         self.reset()
 
     def reset(self):
@@ -97,6 +103,8 @@ class TemporalConsistency:
         output, gt = output.contiguous(), gt.contiguous()
         cur = (self._reduced(output, 1.0), self._reduced(gt, 1.0), self.ops.resize_bilinear(gt, self.h, self.w, 255.0))
         prev, self._prev = self._prev, cur
+        if self.keep_pair:
+            self._last = (cur, prev)
         if prev is None:
             return False
         self.fb = self.flow(cur[2], prev[2])
@@ -105,3 +113,21 @@ class TemporalConsistency:
         self.ops.warp_error(cur[1], prev[1], self.fb, self.ff, out_n=ri[1:2], out3=rf[3:6])
         self.pairs += 1
         return True
+
+    def viz(self, out, which="out", radius=0.0, gain=4.0):
+        """the picture of `Ops.tc_viz` for the frame last pushed, into `out` (fp32 [1,3,2h,2w]): of the pair when that push
+        returned True, of the frame alone (white flow panels, no flags, no error) otherwise.  `which`: "out" draws the output
+        pair, "gt" the ground-truth pair, both against the flows the numbers were taken with.  `radius` > 0: the flow length in
+        reduced-frame pixels that is drawn at full saturation; 0: the larger of the two flows' largest radii, per pair.
+        Nothing synchronises."""
+        assert self.keep_pair and self._last is not None, "viz needs keep_pair=True and a pushed frame"
+        assert which in ("out", "gt") and radius >= 0 and gain >= 0, (which, radius, gain)
+        cur, prev = self._last
+        k = 0 if which == "out" else 1
+        if prev is None:
+            return self.ops.tc_viz(cur[k], None, None, None, None, gain, out=out)
+        if radius > 0:
+            self._radius.fill_(float(radius))
+        else:
+            self.ops.flow_radmax(self.fb, self.ff, h=self.h, w=self.w, out=self._radius)
+        return self.ops.tc_viz(cur[k], prev[k], self.fb, self.ff, self._radius, gain, out=out)
