@@ -569,15 +569,16 @@ def test_conv_bf16_thin_1x1(backend, case):
 
 @pytest.mark.parametrize("case", [(64, 64, "relu", 3), (64, 64, "relu", 0), (48, 48, "lrelu", 1), (9, 64, "relu", 0), (12, 48, "lrelu", 0), (3, 48, "lrelu", 2)], ids=lambda c: "c%d-%d_epi%d" % (c[0], c[1], c[3]))
 def test_conv_bf16_rs_pipeline(backend, case):
-    """Register-stationary persistent kernel with several tiles per workgroup (> 256 tiles): exercises the double-buffered halo
-    and output staging across tile iterations, ragged right and bottom edges, every channel-chunk instantiation."""
+    """Register-stationary persistent kernel with up to two tiles per workgroup (1 022 tiles on 512 workgroups): exercises the
+    double-buffered halo and output staging across one tile hand-over, ragged right and bottom edges, every channel-chunk
+    instantiation.  Deeper tile loops: test_conv_persistent.py."""
     import torch.nn.functional as F
     from importlib import import_module
     CV = import_module("zero-tig_amd.ops").CV
     ops, dev, _ = backend
     Cin, Cout, act, epi = case
     g = torch.Generator().manual_seed(Cin + Cout)
-    H, W = 291, 421          # 37 x 14 = 518 tiles of 8 x 32
+    H, W = 291, 421          # 73 x 14 = 1 022 tiles of 4 x 32
     x = torch.randn(1, Cin, H, W, generator=g).bfloat16().float()
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5
     b = torch.randn(Cout, generator=g) * 0.1

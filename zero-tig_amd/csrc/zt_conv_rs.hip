@@ -8,6 +8,7 @@
 // One barrier per tile.  128-byte pixel rows are XOR-swizzled by (halo column & 7): conflict-free ds_read_b128 for every tap.
 // Channel tails use the K=16 MFMA (48 = 32 + 16, and the thin 3/9/12-channel inputs are a single K=16 chunk).
 #include "zt_conv.h"
+#include <stdlib.h>
 
 namespace {
 
@@ -508,7 +509,9 @@ int zt_launch_conv_rs(ConvArgsH& a, hipStream_t stream) {
   a.tilesX = zt_cdiv(a.Wo, TW);
   a.tilesY = zt_cdiv(a.Ho, 4);
   const int ntiles = a.tilesX * a.tilesY;
-  dim3 grid(ntiles < 512 ? ntiles : 512), block(256);          // two 4-wave workgroups per CU
+  int gx = ntiles < 512 ? ntiles : 512;                        // two 4-wave workgroups per CU
+  if (const char* e = getenv("ZT_CONV_BLOCKS")) gx = atoi(e) > 0 && atoi(e) < gx ? atoi(e) : gx;      // test hook: fewer workgroups, deeper tile loops
+  dim3 grid(gx), block(256);
   const int kc = a.Cin <= 16 ? 0 : (a.Cin > 48 ? 2 : 1);       // 0: one K=16 chunk, 1: 32 + 16, 2: 32 + 32
   if (a.stats) {                                                // fused BatchNorm statistics: the 64 -> 64 layer
     if (!(a.Cout == 64 && kc == 2 && (!a.epi || (a.epi == 3 && a.zprev)))) return ZT_EINVAL;

@@ -1,4 +1,5 @@
 #include "zt_conv.h"
+#include <stdlib.h>
 
 namespace {
 
@@ -229,6 +230,7 @@ int launch_conv_ws(ConvArgsH& a, int NT, int CCH, int pth, hipStream_t stream) {
   int per_cu = 160 * 1024 / (lds + 1024);
   per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
   int gx = ntiles < 256 * per_cu ? ntiles : 256 * per_cu;
+  if (const char* e = getenv("ZT_CONV_BLOCKS")) gx = atoi(e) > 0 && atoi(e) < gx ? atoi(e) : gx;      // test hook: fewer workgroups, deeper tile loops
   dim3 grid(gx, (c16 + NT - 1) / NT), block(64 * pth);
 #define ZT_WS(nt, cch)                                                                               \
   hipLaunchKernelGGL((conv_ws_bf16_kernel<K, nt, cch, 8>), grid, block, 0, stream, a, ntiles);      \

@@ -9,6 +9,7 @@
 //
 // conv2 zero-pads a1: positions of the a1 halo that lie outside the image are stored as 0, not as lrelu(conv1(0) + b1).
 #include "zt_conv.h"
+#include <stdlib.h>
 
 namespace {
 
@@ -259,7 +260,9 @@ extern "C" int zt_denoise_fused_bf16(const float* s0, const float* s1, const flo
   a.H = H; a.W = W; a.ldk1 = ldk1; a.cout = cout;
   a.tilesX = zt_cdiv(W, DN_TW);
   a.ntiles = a.tilesX * zt_cdiv(H, DN_TH);
-  dim3 grid(a.ntiles < 512 ? a.ntiles : 512), block(256);      // two 4-wave workgroups per CU
+  int gx = a.ntiles < 512 ? a.ntiles : 512;                    // two 4-wave workgroups per CU
+  if (const char* e = getenv("ZT_CONV_BLOCKS")) gx = atoi(e) > 0 && atoi(e) < gx ? atoi(e) : gx;      // test hook: fewer workgroups, deeper tile loops
+  dim3 grid(gx), block(256);
   if (ngroups == 1) hipLaunchKernelGGL(denoise_fused_bf16_kernel<1>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(denoise_fused_bf16_kernel<4>, grid, block, 0, stream, a);
   ZT_LAUNCH_CHECK();
