@@ -39,6 +39,9 @@ parser.add_argument("--lpips_weights", type=str, default=None,
 parser.add_argument("--lpips_precision", type=str, default="fp32", choices=["fp32", "bf16"])
 parser.add_argument("--precision", type=str, default=None, choices=["fp32", "bf16"],
                     help="model precision: fp32 = parity mode, bf16 = throughput mode; when not given, ZEROTIG_PRECISION if set, else fp32")
+parser.add_argument("--alternate_corr", type=int, default=0, choices=[0, 1],
+                    help="RAFT's correlation (raft.py:39-40): 0 the all-pairs volume, 1 the on-the-fly lookup from the feature maps, "
+                         "which forms no volume (DESIGN 8l: the volume grows with the fourth power of the frame side)")
 parser.add_argument("--graph", type=int, default=0, choices=[0, 1],
                     help="1: drive the loop through InferStep (weights prepared once, steady-state frames replayed as one hipGraph)")
 parser.add_argument("--device_png", type=int, default=0, choices=[0, 1, 2],
@@ -87,6 +90,9 @@ parser.add_argument("--tc_raft_weights", type=str, default=None,
                          "in the reference, RAFT is never trained there and is built after the weights file is read, so unless your "
                          "checkpoint was made to hold a trained RAFT these are freshly drawn weights (seeded by --seed) and the warping "
                          "error measures little; needs --tc 1")
+parser.add_argument("--tc_alternate_corr", type=int, default=None, choices=[0, 1],
+                    help="the correlation path of the two RAFT runs of --tc 1 (see --alternate_corr); default: the value of "
+                         "--alternate_corr; needs --tc 1")
 parser.add_argument("--tc_viz", type=str, default=None,
                     help="PATH.y4m: one diagnostic picture per frame (DESIGN 8k), 2w x 2h at the reduced size of --tc_scale, 8-bit C420 "
                          "limited range: the colour wheel of the backward and of the forward flow, the denoise result with the pixels "
@@ -126,7 +132,7 @@ def check_y4m_args(args):
             parser.error("--noref 1 grades without ground truth: --hist_match %d cannot be combined with it (there is no histogram "
                          "to match)" % args.hist_match)
     if not args.tc:
-        for flag in ("tc_scale", "tc_raft_weights", "tc_viz", "tc_viz_max", "tc_viz_gain", "tc_flo_dir"):
+        for flag in ("tc_scale", "tc_raft_weights", "tc_alternate_corr", "tc_viz", "tc_viz_max", "tc_viz_gain", "tc_flo_dir"):
             if getattr(args, flag) is not None:
                 parser.error("--%s needs --tc 1" % flag)
     if args.tc_viz is None:
@@ -172,6 +178,8 @@ def check_y4m_args(args):
             args.tc_scale = args.of_scale
         if args.tc_scale < 1:
             parser.error("--tc_scale is an integer >= 1; got %d" % args.tc_scale)
+        if args.tc_alternate_corr is None:
+            args.tc_alternate_corr = args.alternate_corr
         if args.tc_raft_weights is not None and not os.path.isfile(args.tc_raft_weights):
             parser.error("--tc_raft_weights %s: no such file" % args.tc_raft_weights)
         if args.tc_viz is not None:
@@ -302,7 +310,8 @@ def main_y4m(args):
                     raft_w = temporal.load_raft_weights(args.tc_raft_weights, model.raft.state_dict(), dev)
                 else:
                     raft_w = {"raft." + k: v.data for k, v in model.raft.state_dict().items()}
-                tc = temporal.TemporalConsistency(ops, raft_w, dev, H, W, args.tc_scale, model.precision, keep_pair=viz_on)
+                tc = temporal.TemporalConsistency(ops, raft_w, dev, H, W, args.tc_scale, model.precision, keep_pair=viz_on,
+                                                     alternate_corr=bool(args.tc_alternate_corr))
         if viz_on:                                 # the picture: rendered in float, encoded by the kernel of the enhance stream
             viz_head = head.resized(2 * tc.w, 2 * tc.h)._replace(ctag="420mpeg2", color_range="LIMITED")
             viz_fmt = viz_head.format(args.y4m_matrix)

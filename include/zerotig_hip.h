@@ -222,6 +222,21 @@ int zt_corr_lookup(const float* l0, const float* l1, const float* l2, const floa
 int zt_corr_lookup_step(const float* l0, const float* l1, const float* l2, const float* l3, int h, int w, int ld0, const float* coords,
                         void* out, int dt, int ldo, int npx, const float* delta, int ldd, float* coords_out, float* f4, int ldf4,
                         void* fhx, int ldfhx, void* fin, int ldfin, zt_stream_t stream);
+/* ---- on-the-fly correlation (zt_corr_alt.hip; corr.py:63-91 AlternateCorrBlock): the same 4 x 81 window without the volume.
+ * avg_pool2d of the volume == correlation with the equally pooled fmap2, so level l of query n is alpha * <f1[n], P_l[y][x]>.
+ * zt_fmap_pyramid: f2 nhwc [h*w][ld2 >= 256] of storage type dt (256 channels) -> P_1..P_3, fp32 nhwc [hl*wl][256] (floor sizes),
+ * P_{l+1} = (((a + b) + c) + d) * 0.25f of the rounded level below, one launch. */
+int zt_fmap_pyramid(const void* f2, int dt, int ld2, int h, int w, float* p1, float* p2, float* p3, zt_stream_t stream);
+/* zt_corr_lookup / zt_corr_lookup_step with the taps computed from the feature maps: f1 [npx][ld1] and p0 = fmap2 [npx][ld0] of
+ * storage type dt_f (pitches >= 256, multiples of 8), p1..p3 from zt_fmap_pyramid.  From the window coordinate to the output the
+ * arithmetic is zt_corr_lookup's, so the two differ only by the summation order of the dot products; out / dt / ldo and the flow
+ * bookkeeping follow zt_corr_lookup_step (channels >= 324 are never written).  npx == h * w; h, w <= 4096. */
+int zt_corr_alt_lookup(const void* f1, int ld1, const void* p0, int ld0, int dt_f, const float* p1, const float* p2, const float* p3,
+                       int h, int w, float alpha, const float* coords, void* out, int dt, int ldo, int npx, zt_stream_t stream);
+int zt_corr_alt_lookup_step(const void* f1, int ld1, const void* p0, int ld0, int dt_f, const float* p1, const float* p2, const float* p3,
+                            int h, int w, float alpha, const float* coords, void* out, int dt, int ldo, int npx, const float* delta,
+                            int ldd, float* coords_out, float* f4, int ldf4, void* fhx, int ldfhx, void* fin, int ldfin,
+                            zt_stream_t stream);
 /* update.py:42-45: rh = r*h with zr = [z|r]; update.py:47: h = (1-z)h + z q */
 int zt_gru_rh(const void* zr, int dt, int ldzr, const void* hbuf, int ldh, void* rh, int ldrh, int C, int npx, zt_stream_t stream);
 int zt_gru_update(const void* zr, int dt, int ldzr, const void* q, int ldq, void* hbuf, int ldh, int C, int npx, zt_stream_t stream);

@@ -28,6 +28,9 @@ parser.add_argument("--dataset", type=str, default="RLV")
 parser.add_argument("--num_workers", type=int, default=-1, help="decode workers; -1: host cores - 2, at most 12")
 parser.add_argument("--precision", type=str, default=None, choices=["fp32", "bf16"],
                     help="model precision: fp32 = parity mode, bf16 = throughput mode; when not given, ZEROTIG_PRECISION if set, else fp32")
+parser.add_argument("--alternate_corr", type=int, default=0, choices=[0, 1],
+                    help="RAFT's correlation (raft.py:39-40): 0 the all-pairs volume, 1 the on-the-fly lookup from the feature maps, "
+                         "which forms no volume (DESIGN 8l: the volume grows with the fourth power of the frame side)")
 parser.add_argument("--graph", type=int, default=0, choices=[0, 1],
                     help="1: drive the loop through InferStep (weights prepared once, steady-state frames replayed as one hipGraph)")
 

@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node used for training (frame-clip data parallel over RCCL)")
     ap.add_argument("--lpips_weights", type=str, default=None, help="passed to evals.py: LPIPS (VGG) weights file; default: no LPIPS")
     ap.add_argument("--lpips_precision", type=str, default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--alternate_corr", type=int, default=0, choices=[0, 1],
+                    help="passed to train.py and evals.py: 1 = RAFT's on-the-fly correlation lookup, no all-pairs volume (DESIGN 8l)")
     a = ap.parse_args()
     os.makedirs(a.base_exp_dir, exist_ok=True)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s",
@@ -53,11 +55,12 @@ def main():
         os.makedirs(train_dir, exist_ok=True)
         os.makedirs(eval_dir, exist_ok=True)
         dtype = DATASET_TYPES.get(name, name)
+        alt = ["--alternate_corr", "1"] if a.alternate_corr else []
         launcher = [sys.executable] if a.gpus <= 1 else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus),
                                                          "--master-addr", "127.0.0.1"]
         train = launcher + [os.path.join(here, "train.py"), "--dataset", dtype, "--lowlight_images_path", data, "--model_pretrain",
                             os.path.join(a.weights_dir, a.pretrain_weights_file), "--save", train_dir, "--epochs", str(a.epochs),
-                            "--num_workers", str(a.num_workers)]
+                            "--num_workers", str(a.num_workers)] + alt
         if not run(train, log):
             log.error("Training failed for %s. Skipping to next dataset.", name)
             ok_all = False
@@ -70,7 +73,7 @@ def main():
             continue
         lpips_args = ["--lpips_weights", a.lpips_weights, "--lpips_precision", a.lpips_precision] if a.lpips_weights else []
         if not run([sys.executable, os.path.join(here, "evals.py"), "--dataset", dtype, "--lowlight_images_path", data, "--model_pretrain", weights,
-                    "--save", eval_dir] + lpips_args, log):
+                    "--save", eval_dir] + alt + lpips_args, log):
             log.error("Evaluation failed for %s.", name)
             ok_all = False
             continue

@@ -41,6 +41,9 @@ parser.add_argument("--dataset", type=str, default="RLV", help="dataset name")
 parser.add_argument("--num_workers", type=int, default=-1, help="dataloader (decode) workers; -1: host cores - 2, at most 12")
 parser.add_argument("--host_ingest", action="store_true", help="resize + ToTensor on the host like the reference (default: decode only, the rest on the device)")
 parser.add_argument("--precision", type=str, default="bf16", choices=["bf16", "fp32"], help="bf16 throughput mode / fp32 parity mode")
+parser.add_argument("--alternate_corr", type=int, default=0, choices=[0, 1],
+                    help="RAFT's correlation (raft.py:39-40): 0 the all-pairs volume, 1 the on-the-fly lookup from the feature maps, "
+                         "which forms no volume (DESIGN 8l: the volume grows with the fourth power of the frame side)")
 parser.add_argument("--graph", type=int, default=1, help="1: replay the steady-state step from a captured hipGraph (zero-tig_amd/optim.py:TrainStep); 0: eager launches")
 parser.add_argument("--resume", type=str, default=None, help="resume file written every epoch (model + Adam moments + step + loop position)")
 parser.add_argument("--y4m_in", type=str, default=None,

@@ -137,7 +137,7 @@ class RAFT(_Holder):                                       # raft.py:23-48
         if self._plan_cache is None or self._plan_cache[0] != key:
             ops = ops if ops is not None else Ops(get_lib())
             rw = {"raft." + k: v.data for k, v in self.state_dict().items()}
-            self.__dict__["_plan_cache"] = (key, RaftPlan(ops, rw, dev), ops)
+            self.__dict__["_plan_cache"] = (key, RaftPlan(ops, rw, dev, alternate_corr=bool(self.args.alternate_corr)), ops)
         _, plan, ops = self._plan_cache
         _, _, h, w = image1.shape
         Hp, Wp = (h + 7) // 8 * 8, (w + 7) // 8 * 8
@@ -223,7 +223,8 @@ class _ZeroTIGBase(nn.Module):
             self.__dict__["_eng"] = Engine(self._ops, params, bufs, is_WB=getattr(self, "is_WB", False), device=dev,
                                            precision=self.precision)
             rw = {"raft." + k: v.data for k, v in self.raft.state_dict().items()}
-            self.__dict__["_raftplan"] = RaftPlan(self._ops, rw, dev, precision=self.precision)
+            self.__dict__["_raftplan"] = RaftPlan(self._ops, rw, dev, precision=self.precision,
+                                                  alternate_corr=bool(self.raft.args.alternate_corr))    # raft.py:39-40
             self.__dict__["_sig"] = sig
         return self._eng, self._raftplan
 

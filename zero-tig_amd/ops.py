@@ -990,6 +990,34 @@ class Ops:
                       fin, fin.shape[-1], self._s(corr0))
         return out
 
+    # ---- on-the-fly correlation (zt_corr_alt.hip): the same lookup from the feature maps, no volume -----------------
+    def fmap_pyramid(self, fmap2, h, w):
+        """fmap2: nhwc [>= h*w rows][ld >= 256] (fp32 or bf16, 256 channels) -> [P1, P2, P3] fp32 [hl*wl, 256], avg_pool2d(2, 2)
+        with floor sizes, each level from the rounded level below."""
+        f2 = fmap2.view(-1, fmap2.shape[-1])
+        assert f2.shape[0] >= h * w and f2.is_contiguous()
+        dims = [(h // 2, w // 2), (h // 4, w // 4), (h // 8, w // 8)]
+        lv = [torch.empty((a * b, 256), dtype=torch.float32, device=fmap2.device) for a, b in dims]
+        self.lib.call("zt_fmap_pyramid", f2, _dt(f2), f2.shape[-1], h, w, lv[0], lv[1], lv[2], self._s(fmap2))
+        return lv
+
+    def corr_alt_lookup(self, fmap1, fmap2, pyr, h, w, coords, out=None, alpha=1.0 / 16.0):
+        """corr_lookup's output computed from fmap1 / fmap2 ([npx][ld] nhwc views of one storage type) and fmap_pyramid(fmap2)."""
+        if out is None:
+            out = torch.empty((1, h, w, 324), dtype=torch.float32, device=fmap1.device)
+        assert fmap1.dtype == fmap2.dtype
+        self.lib.call("zt_corr_alt_lookup", fmap1, fmap1.shape[-1], fmap2, fmap2.shape[-1], _dt(fmap1), pyr[0], pyr[1], pyr[2], h, w,
+                      float(alpha), coords, out, _dt(out), out.shape[-1], h * w, self._s(fmap1))
+        return out
+
+    def corr_alt_lookup_step(self, fmap1, fmap2, pyr, h, w, coords, out, delta, coords_out, f4, fhx_ptr, ldfhx, fin, alpha=1.0 / 16.0):
+        """corr_alt_lookup at coords + delta with the previous iteration's flow bookkeeping folded in, as corr_lookup_step."""
+        assert fmap1.dtype == fmap2.dtype
+        self.lib.call("zt_corr_alt_lookup_step", fmap1, fmap1.shape[-1], fmap2, fmap2.shape[-1], _dt(fmap1), pyr[0], pyr[1], pyr[2], h, w,
+                      float(alpha), coords, out, _dt(out), out.shape[-1], h * w, delta, 0 if delta is None else delta.shape[-1],
+                      coords_out, f4, f4.shape[-1], fhx_ptr, ldfhx, fin, fin.shape[-1], self._s(fmap1))
+        return out
+
     # ---- bf16 throughput mode of the convolution family ---------------------------------------------------------
     def repack_weight_bf16(self, w, transpose_flip=False, out=None, co_off=0):
         """torch fp32 [Cout,Cin,KH,KW] -> bf16 [KH*KW, CoutP16, ldk8] (input channel fastest); zero padded."""

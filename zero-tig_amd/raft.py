@@ -5,6 +5,7 @@ the convex 8x up-sampling of the last iteration only (the reference computes it 
 
 precision "fp32": exact-fp32 MFMA everywhere (parity mode).  "bf16": feature maps / GRU state / weights bf16 in HBM with fp32
 accumulation; the correlation volume, flow bookkeeping, up-sampling mask and everything downstream (warp) stay fp32."""
+import logging
 import os
 
 import torch
@@ -19,6 +20,20 @@ _ONE_LAUNCH_IN = os.environ.get("ZT_INSTNORM_ONE_LAUNCH", "0") == "1"
 # fused kernel's four DMA -> barrier -> 32-MFMA phases per workgroup are latency-bound at that size; 4K (14 400^2, 1.1 GB) 0.53 ms
 # fused vs 0.39 + 3 x 0.087 = 0.65 ms.  "auto" = fused from 8 000 map pixels up; ZT_FUSED_CORR=1 / 0 force either.
 _FUSED_CORR = os.environ.get("ZT_FUSED_CORR", "auto")
+
+
+def corr_volume_bytes(h, w):
+    """fp32 all-pairs volume of an h x w map with its three pooled levels (corr.py:13-27)"""
+    return 4 * h * w * sum((h >> l) * (w >> l) for l in range(4))
+
+
+def corr_path_line(alternate_corr, h, w):
+    mb = corr_volume_bytes(h, w) / 1e6
+    if alternate_corr:
+        return "RAFT correlation: on-the-fly lookup from the feature maps (--alternate_corr 1), map %d x %d; the all-pairs volume " \
+               "would have taken %.1f MB" % (h, w, mb)
+    return "RAFT correlation: all-pairs volume (--alternate_corr 0), map %d x %d, %.1f MB with its pyramid" % (h, w, mb)
+
 
 class _Side:
     """`with plan._side():` runs the enclosed launches on a second HIP stream, forked from / joined back into the current one
@@ -60,8 +75,11 @@ class RaftPlan:
             torch.cuda.current_stream(self.dev).wait_stream(self._s2)
             self._pending_join = False
 
-    def __init__(self, ops, weights, device, prefix="raft", precision="fp32"):
+    def __init__(self, ops, weights, device, prefix="raft", precision="fp32", alternate_corr=False):
         import os
+        # corr.py:63-91 (args.alternate_corr): the lookup computes its window from the feature maps (zt_corr_alt.hip); no volume
+        self.alternate_corr = bool(alternate_corr)
+        self._said = None
         self.two_streams = os.environ.get("ZT_RAFT_STREAMS", "2") != "1"
         self._s2, self._pending_join = None, False
         """weights: {name: tensor on device} with the reference's `raft.*` state-dict names."""
@@ -208,6 +226,9 @@ class RaftPlan:
         _, Hp, Wp, _ = x2.shape
         h, w = Hp // 8, Wp // 8
         npx = h * w
+        if self._said != (h, w):            # once per map size: which correlation path runs and what the volume takes here
+            self._said = (h, w)
+            logging.getLogger().info(corr_path_line(self.alternate_corr, h, w))     # the scripts' root logger; configures nothing
         # context encoder -> hidden state (tanh) and context (relu) straight into the GRU input buffer: an independent branch
         HX = self._new(1, h, w, 384, zero=True)                              # [net | inp | motion(126) | flow(2)]
         with self._side():
@@ -218,7 +239,12 @@ class RaftPlan:
         # feature encoder (both frames), correlation volume + pyramid
         f = self._encoder("fnet", x2, "instance")
         fmap1 = self._conv(CV(f[0:1]), "fnet.conv2", 256, 1)
-        if self.h:
+        fpyr = None
+        if self.alternate_corr:             # both feature maps nhwc in the storage type + three pooled levels of fmap2 in fp32
+            fmap2 = self._conv(CV(f[1:2]), "fnet.conv2", 256, 1)
+            fpyr = o.fmap_pyramid(fmap2, h, w)
+            corr0 = levels = None
+        elif self.h:
             npxp = (npx + 15) // 16 * 16
             fmap2 = self._new(npxp, 256, zero=True)                         # nhwc == the bf16 weight layout [CoutP][ldk]
             self._conv(CV(f[1:2]), "fnet.conv2", 256, 1, out=fmap2[:npx].view(1, h, w, 256))
@@ -236,6 +262,8 @@ class RaftPlan:
         self._join()
         st = self.new_state(h, w, HX)
         st.corr0, st.levels = corr0, levels
+        if self.alternate_corr:
+            st.fmap1, st.fmap2, st.fpyr = fmap1.view(npx, 256), fmap2.view(npx, 256), fpyr
         aux = {}
         for it in range(iters):
             self.refine_step(st)
@@ -284,11 +312,17 @@ class RaftPlan:
         e, g = "update_block.encoder.", "update_block.gru."
         # (the two halves of the motion encoder are independent too, but a fork / join per iteration costs more than the overlap
         # of two ~20 us branches returns: +6 us per iteration measured with tools/bench_raft.py)
-        if st.pending:
+        fhx = HX.data_ptr() + st.es * 382
+        if self.alternate_corr and st.pending:
+            o.corr_alt_lookup_step(st.fmap1, st.fmap2, st.fpyr, h, w, st.coords1, CORR, st.delta, st.coords2, st.F4, fhx, 384, st.FIN)
+            st.coords1, st.coords2, st.pending = st.coords2, st.coords1, False
+        elif self.alternate_corr:
+            o.corr_alt_lookup(st.fmap1, st.fmap2, st.fpyr, h, w, st.coords1, out=CORR)
+        elif st.pending:
             # the previous iteration's `coords1 += delta_flow` (raft.py:120) rides in this iteration's lookup: it reads coords1 + delta
             # and records the sum (ping-pong buffer) and the flow for the up-sampler / the 7x7 conv / the GRU input, all of which
             # are consumed later in this iteration -- one launch less per iteration than a separate zt_raft_flow_step
-            o.corr_lookup_step(st.corr0, st.levels, h, w, st.coords1, CORR, st.delta, st.coords2, st.F4, HX.data_ptr() + st.es * 382, 384, st.FIN)
+            o.corr_lookup_step(st.corr0, st.levels, h, w, st.coords1, CORR, st.delta, st.coords2, st.F4, fhx, 384, st.FIN)
             st.coords1, st.coords2, st.pending = st.coords2, st.coords1, False
         else:
             o.corr_lookup(st.corr0, st.levels, h, w, st.coords1, out=CORR)

@@ -64,16 +64,17 @@ class TemporalConsistency:
     `fb`, `ff`: the flows last used ([1,2,Hp,Wp], the padded size).
     `keep_pair=True` keeps the reduced frames of the last push (and of its partner), so that `viz` can draw them:
        tc.viz(out, which="out", radius=0.0, gain=4.0)   # the four-panel picture of the last pushed frame into out [1,3,2h,2w]
-    `push` and its numbers are the same either way."""
+    `push` and its numbers are the same either way.
+    `alternate_corr=True`: both RAFT runs look their correlation up from the feature maps and form no all-pairs volume."""
 
-    def __init__(self, ops, raft_weights, dev, H, W, scale, precision, keep_pair=False):
+    def __init__(self, ops, raft_weights, dev, H, W, scale, precision, keep_pair=False, alternate_corr=False):
         why = too_small(H, W, scale)
         if why is not None or scale < 1:
             raise ValueError("TemporalConsistency: scale %d at %dx%d: %s" % (scale, W, H, why or "the scale is an integer >= 1"))
         self.ops, self.dev, self.H, self.W, self.scale = ops, dev, int(H), int(W), int(scale)
         self.h, self.w = self.H // self.scale, self.W // self.scale
         self.Hp, self.Wp = (self.h + 7) // 8 * 8, (self.w + 7) // 8 * 8
-        self.plan = RaftPlan(ops, raft_weights, dev, precision=precision)
+        self.plan = RaftPlan(ops, raft_weights, dev, precision=precision, alternate_corr=alternate_corr)   # DESIGN 8l
         self.plan.two_streams = False
         self.fb = self.ff = None
         self.pairs = 0
