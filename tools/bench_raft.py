@@ -52,4 +52,4 @@ n1 = sum(ops.lib.calls.values())
 plan.run(x2, iters=2)
 n2 = sum(ops.lib.calls.values())
 print("RAFT %s 360x640: %.1f us per call; encoders + corr volume + mask head + upsample %.1f us; refinement %.1f us per iteration "
-      "(%d launches per iteration)" % (prec, t12, t0, (t12 - t0) / 12.0, (n2 - n1) - (n1 - n0) + (n1 - n0) - (n1 - n0) if False else (n2 - n1) - (n1 - n0)))
+      "(%d launches per iteration)" % (prec, t12, t0, (t12 - t0) / 12.0, (n2 - n1) - (n1 - n0)))

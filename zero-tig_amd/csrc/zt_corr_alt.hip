@@ -3,16 +3,16 @@
 // equals the correlation with the equally pooled fmap2 (same floor at odd sizes), so level l of query pixel n is
 //   D_l[y][x] = alpha * < f1[n][0..255], P_l[y][x][0..255] >,   P_0 = fmap2,   P_{l+1} = avg_pool2d(P_l) (fp32, each level from
 //   the rounded level below, zt_fmap_pyramid).
-// Everything from `cx = px / 2^l + (i - 4)` to the output restates corr_lookup_kernel (zt_raft.hip) operation by operation, with
-// taps D_l instead of volume reads: with integer operands the two paths agree bit for bit (tests/test_corr_alt.py).
-#include "zt_common.h"
+// Everything from the window coordinate to the output is corr_lookup_kernel's (zt_raft.hip): both call zt_lookup.h, here with
+// taps D_l instead of volume reads, so with integer operands the two paths agree bit for bit (tests/test_corr_alt.py).
+#include "zt_lookup.h"
 
 namespace {
 
 constexpr int CA_C = 256;        // channels of the feature maps (fnet.conv2)
 constexpr int CA_G = 12;         // side of the integer grid kept per level: 9 window positions + 1 bilinear neighbour + 2 of slack
 
-// P_{l+1}[y][x] = (((P_l[2y][2x] + P_l[2y][2x+1]) + P_l[2y+1][2x]) + P_l[2y+1][2x+1]) * 0.25f: corr_pool_kernel's order.
+// P_{l+1}[y][x] = zt_pool4(P_l[2y][2x], P_l[2y][2x+1], P_l[2y+1][2x], P_l[2y+1][2x+1]): corr_pool_kernel's order.
 // One workgroup per 8 x 8 block of level 0 (= 4 x 4 of level 1, 2 x 2 of level 2, one pixel of level 3), one thread per channel,
 // the three levels in registers.  A cell of level l + 1 exists iff its index is below floor(size_l / 2), and then its four sources
 // exist too, so every read is of a checked cell.
@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(256) fmap_pyramid_kernel(const T* __restrict__
       if (y1 < h1 && x1 < w1) {
         const T* p = f2 + ((size_t)(2 * y1) * w + 2 * x1) * ld2 + c;
         const size_t row = (size_t)w * ld2;
-        v = (((ZtIO<T>::ld(p) + ZtIO<T>::ld(p + ld2)) + ZtIO<T>::ld(p + row)) + ZtIO<T>::ld(p + row + ld2)) * 0.25f;
+        v = zt_pool4(ZtIO<T>::ld(p), ZtIO<T>::ld(p + ld2), ZtIO<T>::ld(p + row), ZtIO<T>::ld(p + row + ld2));
         p1[((size_t)y1 * w1 + x1) * CA_C + c] = v;
       }
       l1[y][x] = v;
@@ -44,12 +44,12 @@ __global__ void __launch_bounds__(256) fmap_pyramid_kernel(const T* __restrict__
       const int y2 = by * 2 + y, x2 = bx * 2 + x;
       float v = 0.f;
       if (y2 < h2 && x2 < w2) {
-        v = (((l1[2 * y][2 * x] + l1[2 * y][2 * x + 1]) + l1[2 * y + 1][2 * x]) + l1[2 * y + 1][2 * x + 1]) * 0.25f;
+        v = zt_pool4(l1[2 * y][2 * x], l1[2 * y][2 * x + 1], l1[2 * y + 1][2 * x], l1[2 * y + 1][2 * x + 1]);
         p2[((size_t)y2 * w2 + x2) * CA_C + c] = v;
       }
       l2[y][x] = v;
     }
-  if (by < h3 && bx < w3) p3[((size_t)by * w3 + bx) * CA_C + c] = (((l2[0][0] + l2[0][1]) + l2[1][0]) + l2[1][1]) * 0.25f;
+  if (by < h3 && bx < w3) p3[((size_t)by * w3 + bx) * CA_C + c] = zt_pool4(l2[0][0], l2[0][1], l2[1][0], l2[1][1]);
 }
 
 struct AltArgs {
@@ -62,13 +62,7 @@ struct AltArgs {
   const float* coords;      // [npx][2] (x, y)
   void* out;                // [npx][ldo], storage type TO
   int npx, ldo;
-  // the flow bookkeeping of the previous refinement iteration, as LookupArgs in zt_raft.hip
-  const float* delta;
-  float* coords_out;
-  float* f4;
-  void* fhx;
-  void* fin;
-  int ldd, ldf4, ldfhx, ldfin, w0;
+  ZtFlowBook book;          // zt_corr_alt_lookup_step: the previous iteration's flow bookkeeping rides in this lookup
 };
 
 // Sums of PV values per lane over groups of lanes in PV + log2 shuffles instead of PV * 6: each step sends the half of the values
@@ -90,17 +84,6 @@ __device__ __forceinline__ void ca_reduce_step(float* v, int lane) {
   }
 }
 
-// the tap coordinate of window position i along one axis: corr_lookup_kernel's sequence (zt_raft.hip), including the clamp that
-// keeps every later index inside [-2, size + 1] for huge, infinite and NaN coordinates
-__device__ __forceinline__ int ca_tap0(float p, int l, int i, int size, float* w1) {
-  float c = p / (float)(1 << l) + (float)(i - 4);
-  float g = 2.f * c / (float)(size - 1) - 1.f;
-  float ic = (g + 1.f) * ((float)(size - 1) / 2.f);
-  float f0 = floorf(ic);
-  *w1 = ic - f0;
-  return (int)fminf(fmaxf(f0, -2.f), (float)size + 1.f);
-}
-
 // One workgroup per query pixel, wave l = pyramid level l.  The wave keeps the query's 256 channels in registers, walks the rows of
 // the integer grid under its 9 x 9 window (at most CA_G x CA_G points, clipped to the map), reads each row as one run of
 // contiguous channels with 16-byte loads per lane (fp32: 64 lanes x 4 channels per point; bf16: 32 lanes x 8 channels, two points
@@ -111,35 +94,17 @@ __global__ void __launch_bounds__(256) corr_alt_lookup_kernel(AltArgs a) {
   const int n = blockIdx.x;
   const int lane = threadIdx.x & 63, l = threadIdx.x >> 6;
   const int H = a.h[l], W = a.w[l];
-  float px = a.coords[(size_t)n * 2 + 0], py = a.coords[(size_t)n * 2 + 1];
-  if (a.delta) {                                                  // same fp32 add as flow_step_kernel: results are bit-identical
-    px += a.delta[(size_t)n * a.ldd + 0];
-    py += a.delta[(size_t)n * a.ldd + 1];
-  }
-  if (threadIdx.x == 0 && a.coords_out) {
-    a.coords_out[(size_t)n * 2 + 0] = px;
-    a.coords_out[(size_t)n * 2 + 1] = py;
-    const float fx = px - (float)(n % a.w0), fy = py - (float)(n / a.w0);
-    if (a.f4) {
-      a.f4[(size_t)n * a.ldf4 + 0] = fx;
-      a.f4[(size_t)n * a.ldf4 + 1] = fy;
-    }
-    if (a.fhx) {
-      ZtIO<TO>::st((TO*)a.fhx + (size_t)n * a.ldfhx + 0, fx);
-      ZtIO<TO>::st((TO*)a.fhx + (size_t)n * a.ldfhx + 1, fy);
-    }
-    if (a.fin) {
-      ZtIO<TO>::st((TO*)a.fin + (size_t)n * a.ldfin + 0, fx);
-      ZtIO<TO>::st((TO*)a.fin + (size_t)n * a.ldfin + 1, fy);
-    }
-  }
-  // The grid this level needs: the tap coordinate is non-decreasing in the window position (every operation of ca_tap0 is
-  // monotonic under rounding), so all taps lie in [tap0(0), tap0(8) + 1].  That span is 10 points, 11 or 12 where the
+  float px, py;
+  zt_lookup_coords(a.coords, a.book, n, &px, &py);
+  if (threadIdx.x == 0 && a.book.coords_out) zt_flow_record<TO>(a.book, n, px, py);
+  // The grid this level needs: the tap coordinate is non-decreasing in the window position (every operation of zt_lookup_tap is
+  // monotonic under rounding), so all taps lie in [tap(0), tap(8) + 1].  That span is 10 points, 11 or 12 where the
   // normalise / de-normalise round trip moves a floor at one end (its error is far below 1 for maps up to 4096, which the launcher
   // requires), and 2 where the clamp has collapsed a far-away window.
   float dummy;
-  const int xmin = ca_tap0(px, l, 0, W, &dummy), ymin = ca_tap0(py, l, 0, H, &dummy);
-  const int xmax = min(ca_tap0(px, l, 8, W, &dummy) + 1, xmin + CA_G - 1), ymax = min(ca_tap0(py, l, 8, H, &dummy) + 1, ymin + CA_G - 1);
+  const int xmin = zt_lookup_tap(px, l, 0, W, &dummy), ymin = zt_lookup_tap(py, l, 0, H, &dummy);
+  const int xmax = min(zt_lookup_tap(px, l, 8, W, &dummy) + 1, xmin + CA_G - 1);
+  const int ymax = min(zt_lookup_tap(py, l, 8, H, &dummy) + 1, ymin + CA_G - 1);
   const int xa = max(xmin, 0), xb = min(xmax, W - 1), ya = max(ymin, 0), yb = min(ymax, H - 1);     // the part inside the map
   const int nx = xb - xa + 1;                                     // <= CA_G; <= 0: nothing of this level is inside
   float* Dl = D[l];
@@ -193,19 +158,12 @@ __global__ void __launch_bounds__(256) corr_alt_lookup_kernel(AltArgs a) {
   for (int r = lane; r < 81; r += 64) {
     const int i = r / 9, j = r - i * 9;
     float wx1, wy1;
-    const int x0 = ca_tap0(px, l, i, W, &wx1), y0 = ca_tap0(py, l, j, H, &wy1);
-    const float wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+    const int x0 = zt_lookup_tap(px, l, i, W, &wx1), y0 = zt_lookup_tap(py, l, j, H, &wy1);
     // a tap inside the map is inside the grid by the argument above; should that ever fail, the result is a NaN, not a wrong number
-#define ZT_TAP(xx, yy)                                                                                                 \
-  (((xx) >= 0 && (xx) < W && (yy) >= 0 && (yy) < H)                                                                    \
-       ? (((xx) - xmin >= 0 && (xx) - xmin < CA_G && (yy) - ymin >= 0 && (yy) - ymin < CA_G) ? Dl[((yy) - ymin) * CA_G + ((xx) - xmin)] \
-                                                                                              : __builtin_nanf("")) \
-       : 0.f)
-    float v = ZT_TAP(x0, y0) * (wx0 * wy0);
-    v = fmaf(ZT_TAP(x0 + 1, y0), wx1 * wy0, v);
-    v = fmaf(ZT_TAP(x0, y0 + 1), wx0 * wy1, v);
-    v = fmaf(ZT_TAP(x0 + 1, y0 + 1), wx1 * wy1, v);
-#undef ZT_TAP
+    const float v = zt_lookup_sample(x0, y0, wx1, wy1, W, H, [&](int xx, int yy) {
+      const int gx = xx - xmin, gy = yy - ymin;
+      return (gx >= 0 && gx < CA_G && gy >= 0 && gy < CA_G) ? Dl[gy * CA_G + gx] : __builtin_nanf("");
+    });
     ZtIO<TO>::st((TO*)a.out + (size_t)n * a.ldo + l * 81 + r, v);
   }
 }
@@ -229,18 +187,10 @@ extern "C" int zt_corr_alt_lookup_step(const void* f1, int ld1, const void* p0, 
   ZT_REQUIRE(f1 && p0 && p1 && p2 && p3 && coords && out && ldo >= 324 && ld1 >= CA_C && ld0 >= CA_C);
   ZT_REQUIRE(ld1 % 8 == 0 && ld0 % 8 == 0);         // 16-byte loads of bf16 rows (fp32 rows need % 4 only)
   ZT_REQUIRE(npx == h * w && h <= 4096 && w <= 4096);
-  ZT_REQUIRE(!coords_out || coords_out != coords);
-  ZT_REQUIRE(!delta || coords_out);                 // a delta that is looked up but not recorded would be lost
   AltArgs a;
+  a.book = {delta, coords_out, f4, fhx, fin, ldd, ldf4, ldfhx, ldfin, w};
+  ZT_REQUIRE(zt_flow_book_ok(a.book, coords) && zt_lookup_levels(h, w, a.h, a.w));
   a.f1 = f1; a.ld1 = ld1; a.p0 = p0; a.ld0 = ld0; a.p[0] = p1; a.p[1] = p2; a.p[2] = p3; a.alpha = alpha;
-  a.delta = delta; a.ldd = ldd; a.coords_out = coords_out; a.f4 = f4; a.ldf4 = ldf4; a.fhx = fhx; a.ldfhx = ldfhx; a.fin = fin;
-  a.ldfin = ldfin; a.w0 = w;
-  int hh = h, ww = w;
-  for (int l = 0; l < 4; ++l) {
-    a.h[l] = hh; a.w[l] = ww;
-    ZT_REQUIRE(hh >= 2 && ww >= 2);        // a 1-pixel level divides by zero in the reference (SURVEY A-13)
-    hh /= 2; ww /= 2;
-  }
   a.coords = coords; a.out = out; a.npx = npx; a.ldo = ldo;
   const dim3 grid((unsigned)npx), block(256);
   if (dt_f == 0 && dt == 0) hipLaunchKernelGGL((corr_alt_lookup_kernel<float, float>), grid, block, 0, stream, a);

@@ -2,7 +2,7 @@
 // down-scale, uint8 truncation + histogram equalisation, replicate padding), correlation pyramid + fused 4-level
 // 9x9 lookup (model/RAFT/corr.py:12-50), SepConvGRU point-wise stages (update.py:33-60), flow bookkeeping and the
 // convex 8x up-sampling (raft.py:64-75).  Convolutions / the correlation GEMM live in zt_conv_tiled.hip.
-#include "zt_common.h"
+#include "zt_lookup.h"
 
 namespace {
 
@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(256) corr_pool_kernel(const float* __restrict_
   int y = (int)((i / wout) % hout);
   long long n = i / ((long long)wout * hout);
   const float* p = src + n * ldin + (size_t)(2 * y) * win + 2 * x;
-  dst[i] = (((p[0] + p[1]) + p[win]) + p[win + 1]) * 0.25f;
+  dst[i] = zt_pool4(p[0], p[1], p[win], p[win + 1]);
 }
 
 struct LookupArgs {
@@ -163,15 +163,7 @@ struct LookupArgs {
   const float* coords;      // [npx][2] (x, y)
   void* out;                // [npx][ldo], fp32 or bf16
   int npx, ldo;
-  // fused flow bookkeeping of the PREVIOUS refinement iteration (raft.py:112-120; zt_corr_lookup_step): the coordinates looked up
-  // are coords + delta, written to coords_out (a different buffer: other threads of the pixel still read coords) together with
-  // flow = coords_out - grid for the up-sampler (f4, fp32) and the two nhwc consumers of the same iteration (fhx, fin; type T)
-  const float* delta;
-  float* coords_out;
-  float* f4;
-  void* fhx;
-  void* fin;
-  int ldd, ldf4, ldfhx, ldfin, w0;
+  ZtFlowBook book;          // zt_corr_lookup_step: the previous iteration's flow bookkeeping rides in this lookup
 };
 
 // corr.py:29-50 + utils.py:285-299: 4 levels x 9x9 window, bilinear, align_corners=True, zeros padding.
@@ -185,44 +177,12 @@ __global__ void __launch_bounds__(256) corr_lookup_kernel(LookupArgs a) {
   int l = ch / 81, r = ch - l * 81;
   int i = r / 9, j = r - i * 9;
   const int H = a.h[l], W = a.w[l];
-  float px = a.coords[n * 2 + 0], py = a.coords[n * 2 + 1];
-  if (a.delta) {                                                  // same fp32 add as flow_step_kernel: results are bit-identical
-    px += a.delta[(size_t)n * a.ldd + 0];
-    py += a.delta[(size_t)n * a.ldd + 1];
-  }
-  if (ch == 0 && a.coords_out) {
-    a.coords_out[n * 2 + 0] = px;
-    a.coords_out[n * 2 + 1] = py;
-    const float fx = px - (float)(n % a.w0), fy = py - (float)(n / a.w0);
-    if (a.f4) {
-      a.f4[(size_t)n * a.ldf4 + 0] = fx;
-      a.f4[(size_t)n * a.ldf4 + 1] = fy;
-    }
-    if (a.fhx) {
-      ZtIO<T>::st((T*)a.fhx + (size_t)n * a.ldfhx + 0, fx);
-      ZtIO<T>::st((T*)a.fhx + (size_t)n * a.ldfhx + 1, fy);
-    }
-    if (a.fin) {
-      ZtIO<T>::st((T*)a.fin + (size_t)n * a.ldfin + 0, fx);
-      ZtIO<T>::st((T*)a.fin + (size_t)n * a.ldfin + 1, fy);
-    }
-  }
-  float cx = px / (float)(1 << l) + (float)(i - 4);
-  float cy = py / (float)(1 << l) + (float)(j - 4);
-  float gx = 2.f * cx / (float)(W - 1) - 1.f;
-  float gy = 2.f * cy / (float)(H - 1) - 1.f;
-  float ix = (gx + 1.f) * ((float)(W - 1) / 2.f);
-  float iy = (gy + 1.f) * ((float)(H - 1) / 2.f);
-  float fx0 = floorf(ix), fy0 = floorf(iy);
-  float wx1 = ix - fx0, wy1 = iy - fy0, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-  int x0 = (int)fminf(fmaxf(fx0, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy0, -2.f), (float)H + 1.f);
+  float px, py, wx1, wy1;
+  zt_lookup_coords(a.coords, a.book, n, &px, &py);
+  if (ch == 0 && a.book.coords_out) zt_flow_record<T>(a.book, n, px, py);
+  const int x0 = zt_lookup_tap(px, l, i, W, &wx1), y0 = zt_lookup_tap(py, l, j, H, &wy1);
   const float* p = a.lvl[l] + (size_t)n * a.ld[l];
-#define ZT_TAP(xx, yy) (((xx) >= 0 && (xx) < W && (yy) >= 0 && (yy) < H) ? p[(size_t)(yy) * W + (xx)] : 0.f)
-  float v = ZT_TAP(x0, y0) * (wx0 * wy0);
-  v = fmaf(ZT_TAP(x0 + 1, y0), wx1 * wy0, v);
-  v = fmaf(ZT_TAP(x0, y0 + 1), wx0 * wy1, v);
-  v = fmaf(ZT_TAP(x0 + 1, y0 + 1), wx1 * wy1, v);
-#undef ZT_TAP
+  const float v = zt_lookup_sample(x0, y0, wx1, wy1, W, H, [&](int xx, int yy) { return p[(size_t)yy * W + xx]; });
   ZtIO<T>::st((T*)a.out + (size_t)n * a.ldo + ch, v);
 }
 
@@ -249,32 +209,14 @@ __global__ void __launch_bounds__(256) gru_update_kernel(const T* __restrict__ z
   ZtIO<T>::st(hbuf + p * ldh + c, (1.f - z) * hv + z * ZtIO<T>::ld(q + p * ldq + c));
 }
 
-// raft.py:112-120: coords1 += delta_flow; flow = coords1 - coords0.  Writes flow to two NHWC destinations.
+// raft.py:112-120: coords1 += delta_flow; flow = coords1 - coords0, as the book says (coords_out == coords: one thread per pixel)
 template <typename T>
-__global__ void __launch_bounds__(256) flow_step_kernel(float* __restrict__ coords1, const float* __restrict__ delta, int ldd,
-                                                        int w, int npx, float* __restrict__ f4, int ldf4,
-                                                        T* __restrict__ fhx, int ldfhx, T* __restrict__ fin, int ldfin) {
+__global__ void __launch_bounds__(256) flow_step_kernel(const float* coords, ZtFlowBook b, int npx) {
   int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= npx) return;
-  float x0 = (float)(n % w), y0 = (float)(n / w);
-  float cx = coords1[n * 2 + 0], cy = coords1[n * 2 + 1];
-  if (delta) {
-    cx += delta[(size_t)n * ldd + 0];
-    cy += delta[(size_t)n * ldd + 1];
-    coords1[n * 2 + 0] = cx;
-    coords1[n * 2 + 1] = cy;
-  }
-  float fx = cx - x0, fy = cy - y0;
-  f4[(size_t)n * ldf4 + 0] = fx;
-  f4[(size_t)n * ldf4 + 1] = fy;
-  if (fhx) {
-    ZtIO<T>::st(fhx + (size_t)n * ldfhx + 0, fx);
-    ZtIO<T>::st(fhx + (size_t)n * ldfhx + 1, fy);
-  }
-  if (fin) {
-    ZtIO<T>::st(fin + (size_t)n * ldfin + 0, fx);
-    ZtIO<T>::st(fin + (size_t)n * ldfin + 1, fy);
-  }
+  float px, py;
+  zt_lookup_coords(coords, b, n, &px, &py);
+  zt_flow_record<T>(b, n, px, py);
 }
 
 __global__ void __launch_bounds__(256) coords_init_kernel(float* __restrict__ coords, int w, int npx) {
@@ -390,18 +332,11 @@ extern "C" int zt_corr_lookup_step(const float* l0, const float* l1, const float
                                    const float* coords, void* out, int dt, int ldo, int npx, const float* delta, int ldd, float* coords_out,
                                    float* f4, int ldf4, void* fhx, int ldfhx, void* fin, int ldfin, hipStream_t stream) {
   ZT_REQUIRE(l0 && l1 && l2 && l3 && coords && out && ldo >= 324);
-  ZT_REQUIRE(!coords_out || coords_out != coords);
-  ZT_REQUIRE(!delta || coords_out);                 // a delta that is looked up but not recorded would be lost
   LookupArgs a;
-  a.delta = delta; a.ldd = ldd; a.coords_out = coords_out; a.f4 = f4; a.ldf4 = ldf4; a.fhx = fhx; a.ldfhx = ldfhx; a.fin = fin;
-  a.ldfin = ldfin; a.w0 = w;
+  a.book = {delta, coords_out, f4, fhx, fin, ldd, ldf4, ldfhx, ldfin, w};
+  ZT_REQUIRE(zt_flow_book_ok(a.book, coords) && zt_lookup_levels(h, w, a.h, a.w));
   a.lvl[0] = l0; a.lvl[1] = l1; a.lvl[2] = l2; a.lvl[3] = l3;
-  int hh = h, ww = w;
-  for (int l = 0; l < 4; ++l) {
-    a.h[l] = hh; a.w[l] = ww; a.ld[l] = l == 0 ? ld0 : hh * ww;
-    ZT_REQUIRE(hh >= 2 && ww >= 2);        // a 1-pixel level divides by zero in the reference (SURVEY A-13)
-    hh /= 2; ww /= 2;
-  }
+  for (int l = 0; l < 4; ++l) a.ld[l] = l == 0 ? ld0 : a.h[l] * a.w[l];
   a.coords = coords; a.out = out; a.npx = npx; a.ldo = ldo;
   long long total = (long long)npx * 324;
   if (dt == 0) hipLaunchKernelGGL(corr_lookup_kernel<float>, dim3((unsigned)zt_cdivl(total, 256)), dim3(256), 0, stream, a);
@@ -447,9 +382,10 @@ extern "C" int zt_raft_coords_init_f32(float* coords, int h, int w, hipStream_t 
 extern "C" int zt_raft_flow_step(float* coords1, const float* delta, int ldd, int h, int w, float* f4, int ldf4, void* fhx,
                                  int ldfhx, void* fin, int ldfin, int dt, hipStream_t stream) {
   ZT_REQUIRE(coords1 && f4);
+  const ZtFlowBook b = {delta, delta ? coords1 : nullptr, f4, fhx, fin, ldd, ldf4, ldfhx, ldfin, w};       // coords1 changes only by a delta
   dim3 grid(zt_cdiv(h * w, 256));
-  if (dt == 0) hipLaunchKernelGGL(flow_step_kernel<float>, grid, dim3(256), 0, stream, coords1, delta, ldd, w, h * w, f4, ldf4, (float*)fhx, ldfhx, (float*)fin, ldfin);
-  else hipLaunchKernelGGL(flow_step_kernel<zt_bf16>, grid, dim3(256), 0, stream, coords1, delta, ldd, w, h * w, f4, ldf4, (zt_bf16*)fhx, ldfhx, (zt_bf16*)fin, ldfin);
+  if (dt == 0) hipLaunchKernelGGL(flow_step_kernel<float>, grid, dim3(256), 0, stream, (const float*)coords1, b, h * w);
+  else hipLaunchKernelGGL(flow_step_kernel<zt_bf16>, grid, dim3(256), 0, stream, (const float*)coords1, b, h * w);
   ZT_LAUNCH_CHECK();
   return ZT_OK;
 }

@@ -40,6 +40,11 @@ def _dt(t):
     return 1 if t.dtype == torch.bfloat16 else 0
 
 
+def _pooled_dims(h, w):
+    """sizes of levels 1..3 of the correlation pyramid over an h x w map: avg_pool2d(2, 2) floors (corr.py:25-27)"""
+    return [(h >> l, w >> l) for l in (1, 2, 3)]
+
+
 ACT = {None: 0, "none": 0, "relu": 1, "lrelu": 2, "sigmoid": 3, "tanh": 4, "sigmoid_clamp": 5}
 
 
@@ -950,14 +955,13 @@ class Ops:
 
     def corr_pyramid(self, corr0, h, w):
         """corr0: NHWC [1,h,w,ld>=h*w] level 0 -> [level1, level2, level3] tensors [npx, hl, wl]."""
-        npx, ld = h * w, corr0.shape[-1]
-        levels, src, hin, win, ldin = [], corr0, h, w, ld
-        for _ in range(3):
-            dst = torch.empty((npx, hin // 2, win // 2), dtype=torch.float32, device=corr0.device)
+        npx = h * w
+        levels, src, hin, win, ldin = [], corr0, h, w, corr0.shape[-1]
+        for hl, wl in _pooled_dims(h, w):
+            dst = torch.empty((npx, hl, wl), dtype=torch.float32, device=corr0.device)
             self.lib.call("zt_corr_pool_f32", src, dst, npx, hin, win, ldin, self._s(corr0))
             levels.append(dst)
-            src, hin, win = dst, hin // 2, win // 2
-            ldin = hin * win
+            src, hin, win, ldin = dst, hl, wl, hl * wl
         return levels
 
     def corr_volume_pyramid_bf16(self, fmap1, fmap2, h, w, alpha):
@@ -967,28 +971,32 @@ class Ops:
         ld0 = (npx + 3) // 4 * 4
         dev = fmap1.device
         corr0 = torch.empty((1, h, w, ld0), dtype=torch.float32, device=dev)
-        dims = [(h // 2, w // 2), (h // 4, w // 4), (h // 8, w // 8)]
-        levels = [torch.empty((npx, a, b), dtype=torch.float32, device=dev) for a, b in dims]
+        levels = [torch.empty((npx, a, b), dtype=torch.float32, device=dev) for a, b in _pooled_dims(h, w)]
         tok = self._ev_begin(self.profile["match"].get((1, 1, 1, 256, npx, h, w))) if self.profile else None
         self.lib.call("zt_corr_volume_pyramid_bf16", fmap1, fmap1.shape[-1], fmap2, fmap2.shape[-1], h, w, float(alpha), corr0, ld0,
                       levels[0], levels[1], levels[2], self._s(fmap1))
         self._ev_end(tok)
         return corr0, levels
 
-    def corr_lookup(self, corr0, levels, h, w, coords, out=None):
-        npx = h * w
+    def _lookup(self, name, head, out, book, stream):
+        """one launch of the lookup entry point `name`; with a book = (delta, coords_out, f4, fhx_ptr, ldfhx, fin), of its _step form:
+        the lookup at coords + delta with the previous iteration's flow bookkeeping folded in (ZtFlowBook, zt_lookup.h)."""
+        if book is not None:
+            delta, coords_out, f4, fhx_ptr, ldfhx, fin = book
+            name += "_step"
+            head += (delta, 0 if delta is None else delta.shape[-1], coords_out, f4, f4.shape[-1], fhx_ptr, ldfhx, fin, fin.shape[-1])
+        self.lib.call(name, *head, stream)
+        return out
+
+    def corr_lookup(self, corr0, levels, h, w, coords, out=None, book=None):
         if out is None:
             out = torch.empty((1, h, w, 324), dtype=torch.float32, device=corr0.device)
-        self.lib.call("zt_corr_lookup", corr0, levels[0], levels[1], levels[2], h, w, corr0.shape[-1], coords, out, _dt(out),
-                      out.shape[-1], npx, self._s(corr0))
-        return out
+        head = (corr0, levels[0], levels[1], levels[2], h, w, corr0.shape[-1], coords, out, _dt(out), out.shape[-1], h * w)
+        return self._lookup("zt_corr_lookup", head, out, book, self._s(corr0))
 
     def corr_lookup_step(self, corr0, levels, h, w, coords, out, delta, coords_out, f4, fhx_ptr, ldfhx, fin):
         """lookup at coords + delta with the previous iteration's flow bookkeeping folded in (zt_corr_lookup_step)."""
-        self.lib.call("zt_corr_lookup_step", corr0, levels[0], levels[1], levels[2], h, w, corr0.shape[-1], coords, out, _dt(out),
-                      out.shape[-1], h * w, delta, 0 if delta is None else delta.shape[-1], coords_out, f4, f4.shape[-1], fhx_ptr, ldfhx,
-                      fin, fin.shape[-1], self._s(corr0))
-        return out
+        return self.corr_lookup(corr0, levels, h, w, coords, out, book=(delta, coords_out, f4, fhx_ptr, ldfhx, fin))
 
     # ---- on-the-fly correlation (zt_corr_alt.hip): the same lookup from the feature maps, no volume -----------------
     def fmap_pyramid(self, fmap2, h, w):
@@ -996,27 +1004,22 @@ class Ops:
         with floor sizes, each level from the rounded level below."""
         f2 = fmap2.view(-1, fmap2.shape[-1])
         assert f2.shape[0] >= h * w and f2.is_contiguous()
-        dims = [(h // 2, w // 2), (h // 4, w // 4), (h // 8, w // 8)]
-        lv = [torch.empty((a * b, 256), dtype=torch.float32, device=fmap2.device) for a, b in dims]
+        lv = [torch.empty((a * b, 256), dtype=torch.float32, device=fmap2.device) for a, b in _pooled_dims(h, w)]
         self.lib.call("zt_fmap_pyramid", f2, _dt(f2), f2.shape[-1], h, w, lv[0], lv[1], lv[2], self._s(fmap2))
         return lv
 
-    def corr_alt_lookup(self, fmap1, fmap2, pyr, h, w, coords, out=None, alpha=1.0 / 16.0):
+    def corr_alt_lookup(self, fmap1, fmap2, pyr, h, w, coords, out=None, alpha=1.0 / 16.0, book=None):
         """corr_lookup's output computed from fmap1 / fmap2 ([npx][ld] nhwc views of one storage type) and fmap_pyramid(fmap2)."""
         if out is None:
             out = torch.empty((1, h, w, 324), dtype=torch.float32, device=fmap1.device)
         assert fmap1.dtype == fmap2.dtype
-        self.lib.call("zt_corr_alt_lookup", fmap1, fmap1.shape[-1], fmap2, fmap2.shape[-1], _dt(fmap1), pyr[0], pyr[1], pyr[2], h, w,
-                      float(alpha), coords, out, _dt(out), out.shape[-1], h * w, self._s(fmap1))
-        return out
+        head = (fmap1, fmap1.shape[-1], fmap2, fmap2.shape[-1], _dt(fmap1), pyr[0], pyr[1], pyr[2], h, w, float(alpha), coords, out,
+                _dt(out), out.shape[-1], h * w)
+        return self._lookup("zt_corr_alt_lookup", head, out, book, self._s(fmap1))
 
     def corr_alt_lookup_step(self, fmap1, fmap2, pyr, h, w, coords, out, delta, coords_out, f4, fhx_ptr, ldfhx, fin, alpha=1.0 / 16.0):
         """corr_alt_lookup at coords + delta with the previous iteration's flow bookkeeping folded in, as corr_lookup_step."""
-        assert fmap1.dtype == fmap2.dtype
-        self.lib.call("zt_corr_alt_lookup_step", fmap1, fmap1.shape[-1], fmap2, fmap2.shape[-1], _dt(fmap1), pyr[0], pyr[1], pyr[2], h, w,
-                      float(alpha), coords, out, _dt(out), out.shape[-1], h * w, delta, 0 if delta is None else delta.shape[-1],
-                      coords_out, f4, f4.shape[-1], fhx_ptr, ldfhx, fin, fin.shape[-1], self._s(fmap1))
-        return out
+        return self.corr_alt_lookup(fmap1, fmap2, pyr, h, w, coords, out, alpha, book=(delta, coords_out, f4, fhx_ptr, ldfhx, fin))
 
     # ---- bf16 throughput mode of the convolution family ---------------------------------------------------------
     def repack_weight_bf16(self, w, transpose_flip=False, out=None, co_off=0):

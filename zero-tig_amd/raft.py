@@ -76,13 +76,12 @@ class RaftPlan:
             self._pending_join = False
 
     def __init__(self, ops, weights, device, prefix="raft", precision="fp32", alternate_corr=False):
-        import os
+        """weights: {name: tensor on device} with the reference's `raft.*` state-dict names."""
         # corr.py:63-91 (args.alternate_corr): the lookup computes its window from the feature maps (zt_corr_alt.hip); no volume
         self.alternate_corr = bool(alternate_corr)
         self._said = None
         self.two_streams = os.environ.get("ZT_RAFT_STREAMS", "2") != "1"
         self._s2, self._pending_join = None, False
-        """weights: {name: tensor on device} with the reference's `raft.*` state-dict names."""
         self.ops, self.lib, self.dev, self.pre = ops, ops.lib, device, prefix
         self.W = dict(weights)
         self.h = precision == "bf16"
@@ -312,20 +311,16 @@ class RaftPlan:
         e, g = "update_block.encoder.", "update_block.gru."
         # (the two halves of the motion encoder are independent too, but a fork / join per iteration costs more than the overlap
         # of two ~20 us branches returns: +6 us per iteration measured with tools/bench_raft.py)
-        fhx = HX.data_ptr() + st.es * 382
-        if self.alternate_corr and st.pending:
-            o.corr_alt_lookup_step(st.fmap1, st.fmap2, st.fpyr, h, w, st.coords1, CORR, st.delta, st.coords2, st.F4, fhx, 384, st.FIN)
-            st.coords1, st.coords2, st.pending = st.coords2, st.coords1, False
-        elif self.alternate_corr:
-            o.corr_alt_lookup(st.fmap1, st.fmap2, st.fpyr, h, w, st.coords1, out=CORR)
-        elif st.pending:
-            # the previous iteration's `coords1 += delta_flow` (raft.py:120) rides in this iteration's lookup: it reads coords1 + delta
-            # and records the sum (ping-pong buffer) and the flow for the up-sampler / the 7x7 conv / the GRU input, all of which
-            # are consumed later in this iteration -- one launch less per iteration than a separate zt_raft_flow_step
-            o.corr_lookup_step(st.corr0, st.levels, h, w, st.coords1, CORR, st.delta, st.coords2, st.F4, fhx, 384, st.FIN)
-            st.coords1, st.coords2, st.pending = st.coords2, st.coords1, False
+        # the previous iteration's `coords1 += delta_flow` (raft.py:120) rides in this iteration's lookup: it reads coords1 + delta
+        # and records the sum (ping-pong buffer) and the flow for the up-sampler / the 7x7 conv / the GRU input, all of which
+        # are consumed later in this iteration -- one launch less per iteration than a separate zt_raft_flow_step
+        book = (st.delta, st.coords2, st.F4, HX.data_ptr() + st.es * 382, 384, st.FIN) if st.pending else None
+        if self.alternate_corr:
+            o.corr_alt_lookup(st.fmap1, st.fmap2, st.fpyr, h, w, st.coords1, CORR, book=book)
         else:
-            o.corr_lookup(st.corr0, st.levels, h, w, st.coords1, out=CORR)
+            o.corr_lookup(st.corr0, st.levels, h, w, st.coords1, CORR, book=book)
+        if st.pending:
+            st.coords1, st.coords2, st.pending = st.coords2, st.coords1, False
         if self.h:      # bf16 mode: the two branches of the motion encoder (update.py:89-94) are independent -> two launches, not four
             o.conv_pair_bf16(CV(CORR, 0, 324), self.wd[e + "convc1"], self._w(e + "convc1.bias"), 256, 1, st.C1,
                              CV(st.FIN, 0, 2), self.wd[e + "convf1"], self._w(e + "convf1.bias"), 128, 7, st.F1, act="relu")
