@@ -6,12 +6,14 @@ default does it) by a radix sort of the output.  LPIPS (VGG, evals.py:73-80, 92-
 user's `lpips.LPIPS(net='vgg').state_dict()` file (zero-tig_amd/lpips.py); without it the two LPIPS fields are null.
 Ground truth: `<...>/input/<scene>/low_light_*/N.png` -> `<...>/gt/<scene>/normal_light_*/N.png` (evals.py:122)."""
 import argparse
+import importlib
 import json
 import logging
 import math
 import os
 import sys
 import time
+import types
 
 import numpy as np
 import torch
@@ -22,7 +24,12 @@ from dataloader.create_data import CreateDataset
 from model.model import Finetunemodel
 from utils import utils
 
-parser = argparse.ArgumentParser("ZERO-IG")
+grading = importlib.import_module("zero-tig_amd.grading")
+scenecut = importlib.import_module("zero-tig_amd.scenecut")
+videorun = importlib.import_module("zero-tig_amd.videorun")
+loe50_grid, noref_values, NR_KEYS = grading.loe50_grid, grading.noref_values, grading.NR_KEYS
+
+parser =argparse.ArgumentParser("ZERO-IG")
 parser.add_argument("--lowlight_images_path", type=str, default="./lowlight_dataset")
 parser.add_argument("--save", type=str, default="./results/BVI-RLV")
 parser.add_argument("--model_pretrain", type=str, default=r"./weights_1.pt")
@@ -108,12 +115,6 @@ parser.add_argument("--tc_flo_dir", type=str, default=None,
                          "Middlebury .flo files at the reduced size, in reduced-frame pixels, numbered by the current frame; needs --tc 1")
 
 CHUNK = 64                                         # frames per read-back of the metric table
-# columns of the metric table's two halves: int64 (exact sums) and float64
-I_SSE, I_SQ, I_SQ_HM, I_COLS = 0, 3, 4, 5
-F_SSIM, F_SSIM_HM, F_SSIM_P, F_LP, F_LP_HM, F_COLS = 0, 1, 2, 5, 10, 15
-I_TC, F_TC = I_COLS, F_COLS                        # --tc 1: two more integers and six more doubles behind them
-NR_I, NR_F = 12, 4                                 # --noref 1: behind those, Ops.noref of the full grid and of the LOE_50 grid
-NR_KEYS = ("LOE", "LOE_50", "L_in", "L_out", "gain", "entropy_in", "entropy_out", "sat_out", "black_out")
 
 
 def check_y4m_args(args):
@@ -163,10 +164,10 @@ def check_y4m_args(args):
     if args.y4m_out == "-":
         parser.error("--y4m_out must be a file: standard output carries the log")
     if args.y4m_size is not None:
-        wh = args.y4m_size.lower().split("x")
-        if len(wh) != 2 or not all(v.isdigit() and int(v) > 0 for v in wh):
+        size = videorun.parse_size(args.y4m_size)
+        if size is None:
             parser.error("--y4m_size takes WxH, e.g. 1920x1080; got %r" % args.y4m_size)
-        args.y4m_size = (int(wh[0]), int(wh[1]))
+        args.y4m_size = size
     if args.y4m_scene_cut < 0:
         parser.error("--y4m_scene_cut is a threshold in [0, 1], 0 = off; got %g" % args.y4m_scene_cut)
     if args.y4m_cuts_json is not None and not args.y4m_scene_cut > 0:
@@ -221,32 +222,52 @@ class GroundTruth:
         return self.ops.yuv_to_planar_f32_sized(self.payload, self.fmt, self.size, out=self.rgb, bufs=self._bufs)
 
 
-def loe50_grid(H, W):
-    """the sample grid of LOE_50: the short side becomes 50, the other side keeps the aspect, each rounded half up"""
-    m = min(H, W)
-    return (100 * H + m) // (2 * m), (100 * W + m) // (2 * m)
+def _plane_format(out_fmt, gt_fmt):
+    """the layout the plane metrics are taken in, or None (one log line says why) when the two payloads cannot be compared"""
+    why = None
+    if (gt_fmt.W, gt_fmt.H, gt_fmt.ss, gt_fmt.depth) != (out_fmt.W, out_fmt.H, out_fmt.ss, out_fmt.depth):
+        why = "the denoise payload is %dx%d %d %d-bit, the ground truth %dx%d %d %d-bit" % (
+            out_fmt.W, out_fmt.H, out_fmt.ss, out_fmt.depth, gt_fmt.W, gt_fmt.H, gt_fmt.ss, gt_fmt.depth)
+    elif min(out_fmt.chroma_shape) < 7 or min(out_fmt.H, out_fmt.W) < 7:
+        why = "a plane is smaller than the 7 x 7 window of SSIM"
+    if why is not None:
+        logging.info("plane metrics off (planes: null): %s", why)
+    return out_fmt if why is None else None
 
 
-def noref_values(full, ents, sub):
-    """the per-frame numbers of --noref 1 from what `Ops.noref` returns on the full grid (six integers `full`, two entropies
-    `ents`) and on the LOE_50 grid (`sub`): [Ns, S_loe, S_a, S_b, n_sat, n_black]"""
-    ns = full[0]
-    l_in, l_out = full[2] / ns, full[3] / ns
-    return {"LOE": full[1] / (ns * (ns - 1)) if ns > 1 else None, "LOE_50": sub[1] / sub[0], "L_in": l_in, "L_out": l_out,
-            "gain": l_out / l_in if full[2] else None, "entropy_in": ents[0], "entropy_out": ents[1], "sat_out": full[4] / ns,
-            "black_out": full[5] / ns}
+def _temporal(args, model, ops, dev, H, W):
+    """--tc 1: the `TemporalConsistency` of the run, or None (the log says why) when the reduced frame is too small for RAFT"""
+    temporal = importlib.import_module("zero-tig_amd.temporal")
+    why = temporal.too_small(H, W, args.tc_scale)
+    if why is not None:
+        logging.info("temporal metrics off (temporal: null): %s", why)
+        if args.tc_viz is not None or args.tc_flo_dir is not None:
+            logging.info("temporal pictures off as well: %s are not written", " and ".join(
+                n for n, v in (("--tc_viz " + str(args.tc_viz), args.tc_viz), ("the .flo files of --tc_flo_dir", args.tc_flo_dir))
+                if v is not None))
+        return None
+    if args.tc_raft_weights is not None:
+        raft_w = temporal.load_raft_weights(args.tc_raft_weights, model.raft.state_dict(), dev)
+    else:
+        raft_w = {"raft." + k: v.data for k, v in model.raft.state_dict().items()}
+    return temporal.TemporalConsistency(ops, raft_w, dev, H, W, args.tc_scale, model.precision, keep_pair=args.tc_viz is not None,
+                                        alternate_corr=bool(args.tc_alternate_corr))
 
 
-def _psnr_of(sq, n):
-    return float("inf") if sq == 0 else 10.0 * math.log10(255.0 ** 2 * n / sq)
+def _read_rows(rows, graders, cut_flags, records):
+    """the rows the table has read back, through every grader: the totals, the log lines and one record per frame"""
+    for i, ri, rf in rows:
+        rec = {"frame": i, "cut": cut_flags[i]}
+        for g in graders:
+            g.read(i + 1, rec, ri, rf)
+        records.append(rec)
 
 
 def main_y4m(args):
     """--y4m_in LOW --y4m_gt GT: the low stream through InferStep(yuv=) as in predict.py, every frame graded against the ground
     truth's; --y4m_in LOW --noref 1: the same loop without a ground-truth reader, every frame graded against its own decoded
-    input.  Each metric kernel writes into a row of a table on the device; the table is read back every CHUNK frames
-    (and at the end), one chunk late, so the host keeps running ahead of the device."""
-    import importlib
+    input.  Each grader's kernels write into a row of the metric table on the device; the table is read back every
+    CHUNK frames (and at the end), one chunk late, so the host keeps running ahead of the device (zero-tig_amd/grading.py)."""
     y4m = importlib.import_module("zero-tig_amd.y4m")
     os.makedirs(args.save, exist_ok=True)
     logging.basicConfig(stream=sys.stdout, level=logging.INFO, format="%(asctime)s %(message)s", datefmt="%m/%d %I:%M:%S %p")
@@ -282,256 +303,77 @@ def main_y4m(args):
         ops = utils._ops()
         out_fmt = step.yuv_format
         gt = None if noref else GroundTruth(ops, gt_fmt, (W, H), dev)
-        planes_on, why = True, None
-        if noref:                                  # no ground-truth payload to hold the planes against
-            planes_on = False
-        elif (gt_fmt.W, gt_fmt.H, gt_fmt.ss, gt_fmt.depth) != (out_fmt.W, out_fmt.H, out_fmt.ss, out_fmt.depth):
-            planes_on = False
-            why = "the denoise payload is %dx%d %d %d-bit, the ground truth %dx%d %d %d-bit" % (
-                out_fmt.W, out_fmt.H, out_fmt.ss, out_fmt.depth, gt_fmt.W, gt_fmt.H, gt_fmt.ss, gt_fmt.depth)
-        elif min(out_fmt.chroma_shape) < 7 or min(out_fmt.H, out_fmt.W) < 7:
-            planes_on, why = False, "a plane is smaller than the 7 x 7 window of SSIM"
-        if not planes_on and not noref:
-            logging.info("plane metrics off (planes: null): %s", why)
-        tc, tc_flags = None, []
-        viz_on, flo_on = False, False
-        if args.tc:
-            temporal = importlib.import_module("zero-tig_amd.temporal")
-            why = temporal.too_small(H, W, args.tc_scale)
-            if why is not None:
-                logging.info("temporal metrics off (temporal: null): %s", why)
-                if args.tc_viz is not None or args.tc_flo_dir is not None:
-                    logging.info("temporal pictures off as well: %s are not written", " and ".join(
-                        n for n, v in (("--tc_viz " + str(args.tc_viz), args.tc_viz), ("the .flo files of --tc_flo_dir", args.tc_flo_dir))
-                        if v is not None))
-            else:
-                viz_on, flo_on = args.tc_viz is not None, args.tc_flo_dir is not None
-                if args.tc_raft_weights is not None:
-                    raft_w = temporal.load_raft_weights(args.tc_raft_weights, model.raft.state_dict(), dev)
-                else:
-                    raft_w = {"raft." + k: v.data for k, v in model.raft.state_dict().items()}
-                tc = temporal.TemporalConsistency(ops, raft_w, dev, H, W, args.tc_scale, model.precision, keep_pair=viz_on,
-                                                     alternate_corr=bool(args.tc_alternate_corr))
-        if viz_on:                                 # the picture: rendered in float, encoded by the kernel of the enhance stream
+        plane_fmt = None if noref else _plane_format(out_fmt, gt_fmt)      # --noref 1: no ground-truth payload to hold the planes against
+        tc = _temporal(args, model, ops, dev, H, W) if args.tc else None
+        tc_extra, viz, flo = {}, None, None
+        if tc is not None and args.tc_viz is not None:
             viz_head = head.resized(2 * tc.w, 2 * tc.h)._replace(ctag="420mpeg2", color_range="LIMITED")
-            viz_fmt = viz_head.format(args.y4m_matrix)
-            viz_rgb = torch.empty((1, 3, 2 * tc.h, 2 * tc.w), dtype=torch.float32, device=dev)
-            viz_yuv = torch.empty(viz_fmt.frame_bytes, dtype=torch.uint8, device=dev)
             viz_writer = y4m.Y4MWriter(args.tc_viz, viz_head)
-        if flo_on:
+            viz = (viz_writer, viz_head.format(args.y4m_matrix), args.tc_viz_max, args.tc_viz_gain)
+            tc_extra["viz"] = {"path": args.tc_viz, "size": [2 * tc.w, 2 * tc.h], "max": args.tc_viz_max, "gain": args.tc_viz_gain}
+        if tc is not None and args.tc_flo_dir is not None:
             os.makedirs(args.tc_flo_dir, exist_ok=True)
             flo_writer = importlib.import_module("zero-tig_amd.flowio").FloWriter()
-        det, cuts, scores, rels = None, [], [], []
-        if args.y4m_scene_cut > 0:
-            det = importlib.import_module("zero-tig_amd.scenecut").SceneCut(ops, dev, fmt, args.y4m_scene_cut)
+            flo, tc_extra["flo_dir"] = (flo_writer, args.tc_flo_dir), args.tc_flo_dir
+        pictures = grading.TemporalPictures(ops, tc, dev, viz, flo) if viz or flo else None
+        det = scenecut.SceneCut(ops, dev, fmt, args.y4m_scene_cut) if args.y4m_scene_cut > 0 else None
+        seq = videorun.Sequences(det, args.y4m_scene_cut)
         if args.y4m_out is not None:
             out_head = head.resized(out_fmt.W, out_fmt.H)._replace(ctag=y4m.ctag_at_depth(head.ctag, out_depth))
             writer = y4m.Y4MWriter(args.y4m_out, out_head)
         lpips_model = utils.lpips_model(args.lpips_weights, dev, args.lpips_precision) if args.lpips_weights else None
         hm_on, lp_on = bool(args.hist_match), lpips_model is not None
-        npix = 3 * H * W
 
-        # the table: two device slots and two pinned host slots, used in turn
-        i_nr, f_nr = I_COLS + (2 if tc else 0), F_COLS + (6 if tc else 0)
-        icols, fcols = i_nr + (NR_I if noref else 0), f_nr + (NR_F if noref else 0)
-        grid50 = loe50_grid(H, W)
-        # no-reference: per key the sum of the frames' values and the number of frames that have one; sum of S_a and of S_b
-        nr_tot, nr_n, nr_s = dict.fromkeys(NR_KEYS, 0.0), dict.fromkeys(NR_KEYS, 0), [0, 0]
-        tab_i = [torch.zeros((CHUNK, icols), dtype=torch.int64, device=dev) for _ in range(2)]
-        tab_f = [torch.zeros((CHUNK, fcols), dtype=torch.float64, device=dev) for _ in range(2)]
-        host_i = [torch.zeros((CHUNK, icols), dtype=torch.int64).pin_memory() for _ in range(2)]
-        host_f = [torch.zeros((CHUNK, fcols), dtype=torch.float64).pin_memory() for _ in range(2)]
-        pending = []                               # (slot, first frame, rows, event) of chunks copied but not yet read
-        records, cut_flags = [], []
-        tot = {"psnr": 0.0, "ssim": 0.0, "lpips": 0.0, "psnr_hm": 0.0, "ssim_hm": 0.0, "lpips_hm": 0.0}
-        sse_tot, ssim_p_tot = [0, 0, 0], [0.0, 0.0, 0.0]
-        # temporal: valid pixels, the three sums of the output and of the ground truth, sum of (MABD - MABD_gt)^2, all over the pairs
-        tc_tot = {"n": 0, "out": [0.0, 0.0, 0.0], "gt": [0.0, 0.0, 0.0], "mabd_sq": 0.0}
-
-        def lp_sum(row, c):
-            return (((row[c] + row[c + 1]) + row[c + 2]) + row[c + 3]) + row[c + 4]
-
-        def grade_noref(n, rec, ri, rf):
-            """frame n of --noref 1 from its row of the table: the record, the totals and the log lines"""
-            full, sub = ri[i_nr:i_nr + 6], ri[i_nr + 6:i_nr + 12]
-            v = noref_values(full, rf[f_nr:f_nr + 2], sub)
-            for key in NR_KEYS:
-                if v[key] is not None:
-                    nr_tot[key] += v[key]
-                    nr_n[key] += 1
-            nr_s[0] += full[2]
-            nr_s[1] += full[3]
-            rec["noref"] = dict(v, ints=full, ints_50=sub)
-            logging.info("NUM: %d, " + ", ".join(key + ": %s" for key in NR_KEYS), n,
-                         *["null" if v[key] is None else "%.4f" % v[key] for key in NR_KEYS])
-            logging.info("Total LOE: %s, Total LOE_50: %.4f, Total L_out: %.4f, Total gain: %s",
-                         "%.4f" % (nr_tot["LOE"] / nr_n["LOE"]) if nr_n["LOE"] else "null", nr_tot["LOE_50"] / n, nr_tot["L_out"] / n,
-                         "%.4f" % (nr_s[1] / nr_s[0]) if nr_s[0] else "null")
-            if args.tc:
-                rec["TC"] = None                   # the first frame of a sequence has no partner
-                if tc is not None and tc_flags[n - 1]:
-                    nv, o3 = ri[I_TC], rf[F_TC:F_TC + 3]
-                    tc_tot["n"] += nv
-                    for q in range(3):
-                        tc_tot["out"][q] += o3[q]
-                    rec["TC"] = {"N": nv, "out": o3, "gt": None}
-                    logging.info("NUM: %d, TC valid: %d, E_warp: %.6f, MABD: %.6f (flows from the output)", n, nv,
-                                 o3[0] / (3 * nv) if nv else float("nan"), o3[2] / (3 * tc.h * tc.w))
-
-        def drain(keep):
-            """read every pending chunk but the newest `keep`: totals, records and the log lines"""
-            while len(pending) > keep:
-                slot, first, rows, event = pending.pop(0)
-                event.synchronize()
-                ri, rf = host_i[slot][:rows].tolist(), host_f[slot][:rows].tolist()
-                for k in range(rows):
-                    n = first + k + 1
-                    rec = {"frame": first + k, "cut": bool(cut_flags[first + k])}
-                    if noref:
-                        grade_noref(n, rec, ri[k], rf[k])
-                        records.append(rec)
-                        continue
-                    psnr, ssim = _psnr_of(ri[k][I_SQ], npix), rf[k][F_SSIM]
-                    tot["psnr"] += psnr
-                    tot["ssim"] += ssim
-                    rec.update(PSNR=psnr, SSIM=ssim)
-                    if not lp_on:
-                        logging.info("NUM: %d, PSNR: %.3f, SSIM: %.3f", n, psnr, ssim)
-                        logging.info("Total PSNR: %.3f, Total SSIM: %.3f", tot["psnr"] / n, tot["ssim"] / n)
-                    else:
-                        lp = lp_sum(rf[k], F_LP)
-                        tot["lpips"] += lp
-                        rec.update(LPIPS=lp)
-                        logging.info("NUM: %d, PSNR: %.3f, SSIM: %.3f, LPIPS: %.3f", n, psnr, ssim, lp)
-                        logging.info("Total PSNR: %.3f, Total SSIM: %.3f, Total LPIPS: %.3f", tot["psnr"] / n, tot["ssim"] / n, tot["lpips"] / n)
-                    if hm_on:
-                        psnr_hm, ssim_hm = _psnr_of(ri[k][I_SQ_HM], npix), rf[k][F_SSIM_HM]
-                        tot["psnr_hm"] += psnr_hm
-                        tot["ssim_hm"] += ssim_hm
-                        rec.update(PSNR_HM=psnr_hm, SSIM_HM=ssim_hm)
-                        if not lp_on:
-                            logging.info("NUM: %d, PSNR_HM: %.3f, SSIM_HM: %.3f", n, psnr_hm, ssim_hm)
-                            logging.info("Total PSNR_HM: %.3f, Total SSIM_HM: %.3f", tot["psnr_hm"] / n, tot["ssim_hm"] / n)
-                        else:
-                            lp_hm = lp_sum(rf[k], F_LP_HM)
-                            tot["lpips_hm"] += lp_hm
-                            rec.update(LPIPS_HM=lp_hm)
-                            logging.info("NUM: %d, PSNR_HM: %.3f, SSIM_HM: %.3f, LPIPS_HM: %.3f", n, psnr_hm, ssim_hm, lp_hm)
-                            logging.info("Total PSNR_HM: %.3f, Total SSIM_HM: %.3f, Total LPIPS_HM: %.3f", tot["psnr_hm"] / n,
-                                         tot["ssim_hm"] / n, tot["lpips_hm"] / n)
-                    if planes_on:
-                        sse, sp = ri[k][I_SSE:I_SSE + 3], rf[k][F_SSIM_P:F_SSIM_P + 3]
-                        for p in range(3):
-                            sse_tot[p] += sse[p]
-                            ssim_p_tot[p] += sp[p]
-                        rec.update(SSE=sse, SSIM_Y=sp[0], SSIM_U=sp[1], SSIM_V=sp[2])
-                        logging.info("NUM: %d, SSE_Y: %d, SSE_U: %d, SSE_V: %d, SSIM_Y: %.3f, SSIM_U: %.3f, SSIM_V: %.3f", n, sse[0], sse[1],
-                                     sse[2], sp[0], sp[1], sp[2])
-                    else:
-                        rec.update(SSE=None, SSIM_Y=None, SSIM_U=None, SSIM_V=None)
-                    if args.tc:
-                        rec["TC"] = None           # the first frame of a sequence has no partner
-                        if tc is not None and tc_flags[first + k]:
-                            nv, o3, g3 = ri[k][I_TC], rf[k][F_TC:F_TC + 3], rf[k][F_TC + 3:F_TC + 6]
-                            tc_tot["n"] += nv
-                            for q in range(3):
-                                tc_tot["out"][q] += o3[q]
-                                tc_tot["gt"][q] += g3[q]
-                            tc_tot["mabd_sq"] += (o3[2] / (3 * tc.h * tc.w) - g3[2] / (3 * tc.h * tc.w)) ** 2
-                            rec["TC"] = {"N": nv, "out": o3, "gt": g3}
-                            logging.info("NUM: %d, TC valid: %d, E_warp: %.6f (gt %.6f), MABD: %.6f (gt %.6f)", n, nv,
-                                         o3[0] / (3 * nv) if nv else float("nan"), g3[0] / (3 * nv) if nv else float("nan"),
-                                         o3[2] / (3 * tc.h * tc.w), g3[2] / (3 * tc.h * tc.w))
-                    records.append(rec)
-
-        def flush(slot, first, rows):
-            host_i[slot].copy_(tab_i[slot], non_blocking=True)
-            host_f[slot].copy_(tab_f[slot], non_blocking=True)
-            event = torch.cuda.Event()
-            event.record()
-            pending.append((slot, first, rows, event))
-
-        frames, gt_frames = 0, 0
+        tab = grading.MetricTable(dev, CHUNK)
+        if noref:
+            graders = [grading.NorefGrader(tab, ops, loe50_grid(H, W))]
+        else:
+            graders = [grading.RgbGrader(tab, ops, 3 * H * W, utils.histogram_match if hm_on else None, lpips_model),
+                       grading.PlaneGrader(tab, ops, plane_fmt)]
+        if args.tc:
+            tc_meta = {"scale": args.tc_scale, "raft": "file" if args.tc_raft_weights else "checkpoint"}
+            temporal_grader = grading.TemporalGrader(tab, tc, noref, tc_meta, tc_extra)
+            graders.append(temporal_grader)
+        tab.build()
+        ctx = types.SimpleNamespace(step=step, output=None, gt=None, gt_yuv=None if noref else gt.payload, cut=False)
+        records, frames, t_first = [], 0, None
         clock = time.perf_counter
         t = {"decode_wait": 0.0, "step": 0.0, "metrics": 0.0, "readback": 0.0, "write": 0.0, "viz": 0.0}
-        t_first = None
         with torch.no_grad():
             while True:
                 t0 = clock()
-                try:
-                    payload = next(reader)
-                except StopIteration:
-                    payload = None
-                try:
-                    gt_payload = payload if noref else next(gt_reader)
-                    gt_frames += 1
-                except StopIteration:
-                    gt_payload = None
+                payload = next(reader, None)
+                gt_payload = payload if noref else next(gt_reader, None)
                 if payload is None or gt_payload is None:
                     if payload is not None or gt_payload is not None:
                         # the longer stream is read to its end, so that the message names both lengths
                         n_in = frames + (0 if payload is None else 1 + sum(1 for _ in reader))
-                        n_gt = gt_frames + (0 if gt_payload is None else sum(1 for _ in gt_reader))
+                        n_gt = frames + (0 if gt_payload is None else 1 + sum(1 for _ in gt_reader))
                         raise ValueError("the streams differ in length: --y4m_in has %d frames, --y4m_gt has %d" % (n_in, n_gt))
                     break
                 t1 = clock()
                 t_first = t1 if t_first is None else t_first
-                is_cut = frames == 0
-                if det is not None:
-                    det.push(payload)
-                    is_cut, score, rel = det.pop()
-                    scores.append(score), rels.append(rel)
-                    if is_cut and frames:
-                        cuts.append(frames)
-                        logging.info("scene cut at frame %d: score %.4f (rel %.4f) > %g", frames, score, rel, args.y4m_scene_cut)
-                    is_cut = is_cut or frames == 0
-                cut_flags.append(det is not None and is_cut and frames > 0)
-                enhance, output, illum = step(payload, is_cut)
+                ctx.cut = seq.next(payload)
+                enhance, ctx.output, illum = step(payload, ctx.cut)
                 reader.release(step.loaded)
                 t2 = clock()
-                slot, row = (frames // CHUNK) & 1, frames % CHUNK
-                ri, rf = tab_i[slot][row], tab_f[slot][row]
-                if noref:                          # step.x: the decoded input after any resize, what the network saw
-                    ops.noref(step.x, output, out_i=ri[i_nr:i_nr + 6], out_f=rf[f_nr:f_nr + 2])
-                    ops.noref(step.x, output, grid=grid50, out_i=ri[i_nr + 6:i_nr + 12], out_f=rf[f_nr + 2:f_nr + 4])
-                    gt_t = output                  # --tc 1: the flows come from the enhanced stream itself
+                if noref:                          # --tc 1: the flows come from the enhanced stream itself
+                    ctx.gt = ctx.output
                 else:
-                    gt_t = gt.load(gt_payload)
+                    ctx.gt = gt.load(gt_payload)
                     gt_reader.release(gt.loaded)
-                    ops.sqdiff_u8(output, gt_t, out=ri[I_SQ:I_SQ + 1])
-                    ops.ssim_u8_dev(output, gt_t, out=rf[F_SSIM:F_SSIM + 1])
-                if lp_on:
-                    gt_feat = lpips_model.features(gt_t)
-                    lpips_model.distance_dev(lpips_model.features(output), gt_feat, rf[F_LP:F_LP + 5])
-                if hm_on:
-                    hm = utils.histogram_match(output, gt_t)
-                    ops.sqdiff_u8(hm, gt_t, out=ri[I_SQ_HM:I_SQ_HM + 1])
-                    ops.ssim_u8_dev(hm, gt_t, out=rf[F_SSIM_HM:F_SSIM_HM + 1])
-                    if lp_on:
-                        lpips_model.distance_dev(lpips_model.features(hm), gt_feat, rf[F_LP_HM:F_LP_HM + 5])
-                if planes_on:
-                    ops.yuv_sse(step.yuv[1], gt.payload, out_fmt, out=ri[I_SSE:I_SSE + 3])
-                    for p in range(3):
-                        ops.ssim_plane(step.yuv[1], gt.payload, out_fmt, p, out=rf[F_SSIM_P + p:F_SSIM_P + p + 1])
-                if tc is not None:
-                    if is_cut:                     # frame 0 and every scene cut: a pair never spans two sequences
-                        tc.reset()
-                    tc_flags.append(tc.push(output, gt_t, ri[I_TC:I_TC + 2], rf[F_TC:F_TC + 6]))
+                ri, rf = tab.row(frames)
+                for g in graders:
+                    g.launch(ctx, ri, rf)
                 t_m = clock()
-                if viz_on:                         # one picture per frame, of the pair or of the frame alone
-                    tc.viz(viz_rgb, "out", args.tc_viz_max, args.tc_viz_gain)
-                    viz_writer.submit(ops.rgb_f32_to_yuv(viz_rgb, viz_fmt, out=viz_yuv))
-                if flo_on and tc_flags[-1]:
-                    for flow, name in ((tc.fb, "bwd"), (tc.ff, "fwd")):
-                        flo_writer.submit(os.path.join(args.tc_flo_dir, "%06d_%s.flo" % (frames, name)), ops.flow_pack(flow, tc.h, tc.w))
+                if pictures is not None:
+                    pictures.submit(frames, temporal_grader.flags[-1])
                 t3 = clock()
                 if writer is not None:
                     writer.submit(step.yuv[0])
                 t4 = clock()
                 frames += 1
-                if frames % CHUNK == 0:
-                    flush(slot, frames - CHUNK, CHUNK)
-                    drain(1)
+                _read_rows(tab.advance(frames), graders, seq.flags, records)
                 t5 = clock()
                 t["decode_wait"] += t1 - t0
                 t["step"] += t2 - t1
@@ -540,68 +382,21 @@ def main_y4m(args):
                 t["write"] += t4 - t3
                 t["readback"] += t5 - t4
             t5 = clock()
-            if frames % CHUNK:
-                flush((frames // CHUNK) & 1, frames - frames % CHUNK, frames % CHUNK)
-            drain(0)
+            _read_rows(tab.finish(), graders, seq.flags, records)
             t_end = clock()                        # every metric of the last frame has been read back
             t["readback"] += t_end - t5
     finally:
-        errors = []
-        for w in (writer, viz_writer, flo_writer):
-            if w is not None:
-                try:
-                    w.close()
-                except BaseException as e:         # noqa: BLE001
-                    errors.append(e)
-        reader.close()
-        if gt_reader is not None:
-            gt_reader.close()
-        if errors and sys.exc_info()[0] is None:
-            raise errors[0]
-    n = max(frames, 1)
-    planes = None
-    if planes_on:
-        hc, wc = out_fmt.chroma_shape
-        samples = [out_fmt.H * out_fmt.W, hc * wc, hc * wc]
-        m = (1 << out_fmt.depth) - 1
-        planes = {"depth": out_fmt.depth, "ss": out_fmt.ss, "samples": samples, "SSE": sse_tot}
-        for p, name in enumerate("YUV"):
-            planes["PSNR_" + name] = 10.0 * math.log10(m * m * samples[p] * frames / sse_tot[p]) if sse_tot[p] else None
-        for p, name in enumerate("YUV"):
-            planes["SSIM_" + name] = ssim_p_tot[p] / n
-    result = {"Total_PSNR": tot["psnr"] / n, "Total_SSIM": tot["ssim"] / n, "Total_LPIPS": tot["lpips"] / n if lp_on else None,
-              "Total_PSNR_HM": tot["psnr_hm"] / n if hm_on else None, "Total_SSIM_HM": tot["ssim_hm"] / n if hm_on else None,
-              "Total_LPIPS_HM": tot["lpips_hm"] / n if lp_on and hm_on else None, "images": frames, "planes": planes}
-    if noref:
-        for k in ("Total_PSNR", "Total_SSIM"):
-            result[k] = None
-        result["noref"] = dict({"graded": "denoise"}, **{k: nr_tot[k] / nr_n[k] if nr_n[k] else None for k in NR_KEYS})
-        result["noref"]["gain"] = nr_s[1] / nr_s[0] if nr_s[0] else None       # of the stream: sum S_b / sum S_a
-        logging.info("no-reference (%d frames, the denoise result against the decoded input): %s", frames,
-                     ", ".join("%s: %s" % (k, "null" if result["noref"][k] is None else "%.6g" % result["noref"][k]) for k in NR_KEYS))
+        videorun.close_streams((writer, viz_writer, flo_writer), (reader, gt_reader))
+    result = dict.fromkeys(("Total_PSNR", "Total_SSIM", "Total_LPIPS", "Total_PSNR_HM", "Total_SSIM_HM", "Total_LPIPS_HM"))
+    result.update(images=frames, planes=None)
+    if noref:                                      # every key in its place before the graders fill theirs in
+        result["noref"] = None
     if det is not None:
-        result["cuts"] = cuts
+        result["cuts"] = seq.cuts
     if args.tc:
         result["temporal"] = None
-        if tc is not None:
-            pairs, px = sum(tc_flags), tc.h * tc.w
-            te = {"scale": args.tc_scale, "size": [tc.w, tc.h], "pairs": pairs, "raft": "file" if args.tc_raft_weights else "checkpoint",
-                  "valid_share": tc_tot["n"] / (pairs * px) if pairs else None}
-            for sfx, s3 in (("", tc_tot["out"]), ("_gt", tc_tot["gt"])):
-                te["E_warp" + sfx] = s3[0] / (3 * tc_tot["n"]) if tc_tot["n"] else None
-                te["E_static" + sfx] = s3[1] / (3 * pairs * px) if pairs else None
-                te["MABD" + sfx] = s3[2] / (3 * pairs * px) if pairs else None
-            te["MABD_mse"] = tc_tot["mabd_sq"] / pairs if pairs else None
-            if noref:                              # the output was pushed in the ground truth's place: those numbers repeat the output's
-                te.update(E_warp_gt=None, E_static_gt=None, MABD_gt=None, MABD_mse=None, flow_from="output")
-            if viz_on:
-                te["viz"] = {"path": args.tc_viz, "size": [2 * tc.w, 2 * tc.h], "max": args.tc_viz_max, "gain": args.tc_viz_gain}
-            if flo_on:
-                te["flo_dir"] = args.tc_flo_dir
-            result["temporal"] = te
-            logging.info("temporal (scale %d, %d pairs): %s", args.tc_scale, pairs,
-                         ", ".join("%s: %s" % (k, "null" if te[k] is None else "%.6g" % te[k]) for k in
-                                   ("valid_share", "E_warp", "E_warp_gt", "E_static", "E_static_gt", "MABD", "MABD_gt", "MABD_mse")))
+    for g in graders:
+        g.summary(result)
     with open(os.path.join(args.save, "Metrics.json"), "w") as fh:
         json.dump(result, fh)
     if args.y4m_frames_json:
@@ -609,18 +404,19 @@ def main_y4m(args):
             json.dump(records, fh)
     if args.y4m_cuts_json:
         with open(args.y4m_cuts_json, "w") as fh:
-            json.dump({"threshold": args.y4m_scene_cut, "cuts": cuts, "score": scores, "rel": rels}, fh)
+            json.dump(seq.cuts_json(), fh)
     if args.timing_json and frames:
         per = {k + "_ms": 1e3 * v / frames for k, v in t.items() if k != "viz"}
-        if viz_on or flo_on:                       # the time `submit` waited for a free slot is part of viz_ms
+        if pictures is not None:                   # the time `submit` waited for a free slot is part of viz_ms
             per["viz"] = {"viz_ms": 1e3 * t["viz"] / frames,
                           "wait_writer_ms": 1e3 * sum(w.wait_writer for w in (viz_writer, flo_writer) if w is not None) / frames}
         with open(args.timing_json, "w") as fh:
             json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), graph=args.graph, y4m=1,
-                           hist_match=int(hm_on), lpips=int(lp_on), planes=int(planes_on), **({"noref": 1} if noref else {}),
+                           hist_match=int(hm_on), lpips=int(lp_on), planes=int(plane_fmt is not None), **({"noref": 1} if noref else {}),
                            scene_wait_ms=1e3 * det.wait / frames if det is not None else None,
                            **({"tc": int(tc is not None), "tc_scale": args.tc_scale} if args.tc else {})), fh)
     logging.info("Total frame number: %d", frames)
+
 
 
 def main():

@@ -17,6 +17,8 @@ from model.model import Finetunemodel
 from utils import utils
 from utils.utils import sequential_judgment
 
+videorun = __import__("importlib").import_module("zero-tig_amd.videorun")
+
 parser = argparse.ArgumentParser("ZERO-TIG")
 parser.add_argument("--lowlight_images_path", type=str, default="./data")
 parser.add_argument("--save", type=str, default="./results/")
@@ -104,10 +106,10 @@ def main_y4m(args):
     step = importlib.import_module("zero-tig_amd.infer").InferStep(model, use_graph=True, ingest_size=(1920, 1080) if args.y4m_resize else None,
                                                                    yuv=fmt, yuv_out_depth=out_depth, yuv_size=args.y4m_size)
     out_head = head.resized(step.yuv_format.W, step.yuv_format.H)._replace(ctag=y4m.ctag_at_depth(head.ctag, out_depth))
-    det, cuts, scores, rels = None, [], [], []
+    det = None
     if args.y4m_scene_cut > 0:
-        det = importlib.import_module("zero-tig_amd.scenecut").SceneCut(
-            importlib.import_module("zero-tig_amd.ops").Ops(importlib.import_module("zero-tig_amd.lib").get_lib()), dev, fmt, args.y4m_scene_cut)
+        det = importlib.import_module("zero-tig_amd.scenecut").SceneCut(utils._ops(), dev, fmt, args.y4m_scene_cut)
+    seq = videorun.Sequences(det, args.y4m_scene_cut)
     if args.y4m_out is not None:
         writers = [y4m.Y4MWriter(args.y4m_out, out_head, fh=sink)]
     else:
@@ -127,16 +129,7 @@ def main_y4m(args):
                     break
                 t1 = clock()
                 t_first = t1 if t_first is None else t_first
-                if det is None:
-                    step(payload, frames == 0)
-                else:                              # the detector's own stream; its copy has completed when pop() returns
-                    det.push(payload)
-                    is_cut, score, rel = det.pop()
-                    scores.append(score), rels.append(rel)
-                    if is_cut and frames:
-                        cuts.append(frames)
-                        logging.info("scene cut at frame %d: score %.4f (rel %.4f) > %g", frames, score, rel, args.y4m_scene_cut)
-                    step(payload, frames == 0 or is_cut)
+                step(payload, seq.next(payload))
                 reader.release(step.loaded)        # the ring buffer is free once the copy to the device has run
                 t2 = clock()
                 for w, p in zip(writers, step.yuv):    # the copies are ordered on the stream: the next step may overwrite the buffers
@@ -147,19 +140,11 @@ def main_y4m(args):
                 t["step"] += t2 - t1
                 t["write"] += t4 - t2
     finally:
-        errors = []
-        for w in writers:                          # every stream is drained; the first failure is the one reported
-            try:
-                w.close()
-            except BaseException as e:             # noqa: BLE001
-                errors.append(e)
-        reader.close()
-        if errors and sys.exc_info()[0] is None:
-            raise errors[0]
+        videorun.close_streams(writers, [reader])
     print("Total frame number: ", frames)
     if args.y4m_cuts_json:
         with open(args.y4m_cuts_json, "w") as fh:
-            json.dump({"threshold": args.y4m_scene_cut, "cuts": cuts, "score": scores, "rel": rels}, fh)
+            json.dump(seq.cuts_json(), fh)
     if args.timing_json and frames:
         t_end = clock()                            # the last stream has been closed
         t["writer_wait"] = sum(w.wait_writer for w in writers)
@@ -170,7 +155,7 @@ def main_y4m(args):
         extra = {}
         if det is not None:                        # part of `step`: the seconds pop() was blocked
             t["scene_wait"] = det.wait
-            extra["cuts"] = len(cuts)
+            extra["cuts"] = len(seq.cuts)
         per = {k + "_ms": 1e3 * v / frames for k, v in t.items()}
         with open(args.timing_json, "w") as fh:
             json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), device_png=0, graph=args.graph,
@@ -187,10 +172,10 @@ def main():
         if args.y4m_resize:
             parser.error("--y4m_size cannot be combined with --y4m_resize 1: the first is the float resize to WxH, the second the "
                          "loaders' 8-bit resize to 1920x1080")
-        wh = args.y4m_size.lower().split("x")
-        if len(wh) != 2 or not all(v.isdigit() and int(v) > 0 for v in wh):
+        size = videorun.parse_size(args.y4m_size)
+        if size is None:
             parser.error("--y4m_size takes WxH, e.g. 1920x1080; got %r" % args.y4m_size)
-        args.y4m_size = (int(wh[0]), int(wh[1]))
+        args.y4m_size = size
     if args.y4m_out_depth and args.y4m_in is None:
         parser.error("--y4m_out_depth needs --y4m_in")
     if args.y4m_scene_cut < 0:

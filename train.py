@@ -25,6 +25,7 @@ from utils import utils
 optim = __import__("importlib").import_module("zero-tig_amd.optim")
 y4m = __import__("importlib").import_module("zero-tig_amd.y4m")
 scenecut = __import__("importlib").import_module("zero-tig_amd.scenecut")
+videorun = __import__("importlib").import_module("zero-tig_amd.videorun")
 
 parser = argparse.ArgumentParser("ZERO-TIG")
 parser.add_argument("--batch_size", type=int, default=1, help="batch size (frames per GPU per step; the recurrent cache needs 1)")
@@ -68,14 +69,6 @@ def save_images(tensor):
     return utils.quantize_u8(tensor).cpu().numpy()
 
 
-def parse_size(text):
-    """'WxH' -> (W, H), or None when it is not two positive integers"""
-    parts = text.lower().split("x")
-    if len(parts) != 2 or not all(p.isdigit() and int(p) > 0 for p in parts):
-        return None
-    return int(parts[0]), int(parts[1])
-
-
 def check_y4m_args(args, world):
     """the refusals of the --y4m_* flags (parser.error: exit status 2, before anything touches the GPU)"""
     if args.y4m_in is None:
@@ -89,7 +82,7 @@ def check_y4m_args(args, world):
         parser.error("--y4m_in - is read once: it needs --epochs 1 and one rank (got --epochs %d, %d ranks); use a file" % (args.epochs, world))
     if args.y4m_scene_cut is not None and args.y4m_scene_cut < 0:
         parser.error("--y4m_scene_cut is a threshold in [0, 1], 0 = off; got %g" % args.y4m_scene_cut)
-    if args.y4m_size is not None and parse_size(args.y4m_size) is None:
+    if args.y4m_size is not None and videorun.parse_size(args.y4m_size) is None:
         parser.error("--y4m_size takes WxH, e.g. 1920x1080; got %r" % args.y4m_size)
     if args.y4m_preview < -1:
         parser.error("--y4m_preview takes -1 (all frames), 0 (none) or a frame count; got %d" % args.y4m_preview)
@@ -105,28 +98,23 @@ def y4m_result_pass(args, ops, model, dev, fmt, size, head, epoch):
     reader = y4m.Y4MReader(args.y4m_in, count=None if args.y4m_preview < 0 else args.y4m_preview)
     writers = [y4m.Y4MWriter(os.path.join(args.save, "result", "%s_%s_%d.y4m" % (stem, kind, epoch)), out_head) for kind in ("enhance", "denoise")]
     det = scenecut.SceneCut(ops, dev, fmt, args.y4m_scene_cut) if args.y4m_scene_cut else None
+    seq = videorun.Sequences(det, args.y4m_scene_cut, log=False)       # the cuts are logged by the training loop alone
     bufs = ops.sized_bufs(fmt, size, dev) if size != (fmt.W, fmt.H) else None
     payload_dev = torch.empty(fmt.frame_bytes, dtype=torch.uint8, device=dev)
     try:
         with torch.no_grad():
-            for it, payload in enumerate(reader):
-                cut = False
-                if det is not None:
-                    det.push(payload)
-                    cut = det.pop()[0]
+            for payload in reader:
+                model.is_new_seq = seq.next(payload)
                 payload_dev.copy_(payload, non_blocking=True)
                 loaded = torch.cuda.Event()
                 loaded.record()
                 reader.release(loaded)
                 x = ops.yuv_to_planar_f32(payload_dev, fmt) if bufs is None else ops.yuv_to_planar_f32_sized(payload_dev, fmt, size, bufs=bufs)
-                model.is_new_seq = it == 0 or cut
                 outs = model(x)
                 for w, t in zip(writers, (outs[6], outs[13])):
                     w.submit(ops.rgb_f32_to_yuv(t.detach().contiguous().float(), out_fmt))
     finally:
-        reader.close()
-        for w in writers:
-            w.close()
+        videorun.close_streams(writers, [reader])
 
 
 def main_y4m(args, model, optimizer, dev, rank, world, model_path):
@@ -148,26 +136,20 @@ def main_y4m(args, model, optimizer, dev, rank, world, model_path):
         if stepper is None:
             head = reader.header
             fmt = head.format(matrix)
-            size = (fmt.W, fmt.H) if args.y4m_size is None else parse_size(args.y4m_size)
+            size = (fmt.W, fmt.H) if args.y4m_size is None else videorun.parse_size(args.y4m_size)
             logging.info("Y4M input: %dx%d C%s %d-bit %s %s, trained at %dx%d, frames %d.. of this rank",
                          head.W, head.H, head.ctag, fmt.depth, "full" if head.full else "limited", matrix, size[0], size[1], first)
             stepper = optim.TrainStep(model, optimizer, use_graph=bool(args.graph), yuv=fmt, yuv_size=size)
         det = scenecut.SceneCut(ops, dev, fmt, args.y4m_scene_cut) if args.y4m_scene_cut else None
+        seq = videorun.Sequences(det, args.y4m_scene_cut, first=first)
         losses = []
         t_epoch = time.perf_counter()
         try:
             for it, payload in enumerate(reader):
                 if steps_per_epoch is not None and it >= steps_per_epoch:
                     break
-                new_seq = it == 0
-                if det is not None:                # the detector's own stream; its copy has completed when pop() returns
-                    det.push(payload)
-                    is_cut, score, rel = det.pop()
-                    if is_cut and it:
-                        logging.info("scene cut at frame %d: score %.4f (rel %.4f) > %g", first + it, score, rel, args.y4m_scene_cut)
-                        new_seq = True
                 total_step += 1
-                loss = stepper(payload, is_new_seq=new_seq)
+                loss = stepper(payload, is_new_seq=seq.next(payload))
                 reader.release(stepper.loaded)     # the ring buffer is free once the copy to the device has run
                 losses.append(loss.item())
                 logging.info("train-epoch %03d %03d %f", epoch, it, losses[-1])

@@ -1,0 +1,315 @@
+"""The grading of evals.py's video mode: the metric table the kernels write into, and one grader per family of
+metrics.  A grader registers its columns with the table, and then
+  launch(ctx, ri, rf)    queues the frame's kernels, which write into its columns of the device row (ri, rf); never synchronises
+  read(n, rec, ri, rf)   host only, one chunk later: the same row as lists -> totals, the frame's record `rec`, the log lines of
+                         frame n (counted from 1)
+  summary(result)        its keys of Metrics.json (result["images"] is the frame count) and its closing log line
+`ctx`: the frame as the loop holds it -- step (the InferStep), output and gt ([1,3,H,W] on the device), gt_yuv (the ground truth's
+payload on the device), cut (the frame starts a sequence).  Everything of the project a grader calls is handed to it."""
+import logging
+import math
+import os
+import types
+
+import torch
+
+NR_KEYS = ("LOE", "LOE_50", "L_in", "L_out", "gain", "entropy_in", "entropy_out", "sat_out", "black_out")
+
+
+class MetricTable:
+    """One row per frame, an int64 half (exact sums) and a float64 half, in two device slots of `chunk` rows used in turn, each
+    with a pinned host twin.  Columns first: `tab.ints(name, width)` / `tab.floats(name, width)` -> the slice of that half's row,
+    of a device row and of a read-back row alike; then `build()`.  `row(frame)` -> the device row (ri, rf) the frame's kernels
+    write into.  `advance(frames_done)` after every frame: a full chunk is copied to its host twin behind the kernels, and the
+    chunk before it is read -- never the one just copied, so the host keeps running ahead of the device.  `finish()` copies the
+    tail and reads everything left.  Both return the rows read, [(frame, ri, rf)] as lists, in frame order, each frame once."""
+
+    def __init__(self, dev, chunk):
+        self.dev, self.chunk = dev, int(chunk)
+        self.names, self.width = set(), {torch.int64: 0, torch.float64: 0}
+        self.slots = None
+        self.pending = []                          # (slot, first frame, rows, event) of chunks copied but not yet read
+        self.done, self.flushed = 0, 0             # frames written, frames copied to the host
+
+    def _column(self, dtype, name, width):
+        assert self.slots is None and name not in self.names, name
+        self.names.add(name)
+        start = self.width[dtype]
+        self.width[dtype] = start + width
+        return slice(start, start + width)
+
+    def ints(self, name, width):
+        return self._column(torch.int64, name, width)
+
+    def floats(self, name, width):
+        return self._column(torch.float64, name, width)
+
+    def build(self):
+        halves = [(self.chunk, w, dt) for dt, w in self.width.items()]
+        self.slots = [[torch.zeros((r, w), dtype=dt, device=self.dev) for r, w, dt in halves] for _ in range(2)]
+        self.host = [[torch.zeros((r, w), dtype=dt).pin_memory() for r, w, dt in halves] for _ in range(2)]
+        return self
+
+    def row(self, frame):
+        ti, tf = self.slots[(frame // self.chunk) & 1]
+        return ti[frame % self.chunk], tf[frame % self.chunk]
+
+    def _flush(self, first, rows):
+        slot = (first // self.chunk) & 1
+        for h, d in zip(self.host[slot], self.slots[slot]):
+            h.copy_(d, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        self.pending.append((slot, first, rows, event))
+        self.flushed = first + rows
+
+    def _drain(self, keep):
+        out = []
+        while len(self.pending) > keep:
+            slot, first, rows, event = self.pending.pop(0)
+            event.synchronize()
+            ri, rf = (h[:rows].tolist() for h in self.host[slot])
+            out.extend((first + k, ri[k], rf[k]) for k in range(rows))
+        return out
+
+    def advance(self, frames_done):
+        self.done = frames_done
+        if frames_done - self.flushed < self.chunk:
+            return []
+        self._flush(self.flushed, self.chunk)
+        return self._drain(1)
+
+    def finish(self):
+        if self.done > self.flushed:
+            self._flush(self.flushed, self.done - self.flushed)
+        return self._drain(0)
+
+
+def _psnr_of(sq, n):
+    return float("inf") if sq == 0 else 10.0 * math.log10(255.0 ** 2 * n / sq)
+
+
+class RgbGrader:
+    """PSNR (an exact integer sum) and SSIM of the output against the ground truth; with `lpips` (the model of
+    zero-tig_amd/lpips.py) LPIPS as five layer sums, added on the host; with `hist_match` (f(output, gt) -> the matched frame)
+    the same numbers of the matched frame as *_HM."""
+
+    def __init__(self, tab, ops, npix, hist_match=None, lpips=None):
+        self.ops, self.npix, self.hist_match, self.lpips = ops, npix, hist_match, lpips
+        self.passes, self.tot = [], {}             # the output itself, then the matched frame; key -> sum over the frames
+        for sfx in ("", "_HM") if hist_match else ("",):
+            keys = [k + sfx for k in ("PSNR", "SSIM") + (("LPIPS",) if lpips else ())]
+            self.passes.append(types.SimpleNamespace(
+                matched=bool(sfx), sq=tab.ints("sq" + sfx, 1), ssim=tab.floats("ssim" + sfx, 1),
+                lpips=tab.floats("lpips" + sfx, 5) if lpips else None, keys=keys,
+                line="NUM: %d, " + ", ".join(k + ": %.3f" for k in keys), total_line=", ".join("Total " + k + ": %.3f" for k in keys)))
+            self.tot.update(dict.fromkeys(keys, 0.0))
+
+    def launch(self, ctx, ri, rf):
+        gt_feat = None
+        for p in self.passes:
+            x = self.hist_match(ctx.output, ctx.gt) if p.matched else ctx.output
+            self.ops.sqdiff_u8(x, ctx.gt, out=ri[p.sq])
+            self.ops.ssim_u8_dev(x, ctx.gt, out=rf[p.ssim])
+            if p.lpips is not None:                # the ground truth's features serve both passes
+                gt_feat = self.lpips.features(ctx.gt) if gt_feat is None else gt_feat
+                self.lpips.distance_dev(self.lpips.features(x), gt_feat, rf[p.lpips])
+
+    def read(self, n, rec, ri, rf):
+        tot = self.tot
+        for p in self.passes:
+            values = [_psnr_of(ri[p.sq][0], self.npix), rf[p.ssim][0]]
+            if p.lpips is not None:
+                a = rf[p.lpips]
+                values.append((((a[0] + a[1]) + a[2]) + a[3]) + a[4])
+            for k, x in zip(p.keys, values):
+                tot[k] += x
+                rec[k] = x
+            logging.info(p.line, n, *values)
+            logging.info(p.total_line, *[tot[k] / n for k in p.keys])
+
+    def summary(self, result):
+        for k, x in self.tot.items():
+            result["Total_" + k] = x / max(result["images"], 1)
+
+
+class PlaneGrader:
+    """the SSE and SSIM of the three planes of the denoise payload against the ground truth's, which has its layout `fmt`;
+    fmt None: the layouts differ, every field is null"""
+
+    def __init__(self, tab, ops, fmt):
+        self.ops, self.fmt = ops, fmt
+        if fmt is not None:
+            self.sse, self.ssim = tab.ints("plane_sse", 3), [tab.floats("plane_ssim_" + name, 1) for name in "YUV"]
+        self.sse_tot, self.ssim_tot = [0, 0, 0], [0.0, 0.0, 0.0]
+
+    def launch(self, ctx, ri, rf):
+        if self.fmt is not None:
+            self.ops.yuv_sse(ctx.step.yuv[1], ctx.gt_yuv, self.fmt, out=ri[self.sse])
+            for p in range(3):
+                self.ops.ssim_plane(ctx.step.yuv[1], ctx.gt_yuv, self.fmt, p, out=rf[self.ssim[p]])
+
+    def read(self, n, rec, ri, rf):
+        if self.fmt is None:
+            rec.update(SSE=None, SSIM_Y=None, SSIM_U=None, SSIM_V=None)
+            return
+        sse, sp = ri[self.sse], [rf[s][0] for s in self.ssim]
+        for p in range(3):
+            self.sse_tot[p] += sse[p]
+            self.ssim_tot[p] += sp[p]
+        rec.update(SSE=sse, SSIM_Y=sp[0], SSIM_U=sp[1], SSIM_V=sp[2])
+        logging.info("NUM: %d, SSE_Y: %d, SSE_U: %d, SSE_V: %d, SSIM_Y: %.3f, SSIM_U: %.3f, SSIM_V: %.3f", n, *sse, *sp)
+
+    def summary(self, result):
+        if self.fmt is None:
+            return
+        fmt, frames = self.fmt, result["images"]
+        hc, wc = fmt.chroma_shape
+        samples = [fmt.H * fmt.W, hc * wc, hc * wc]
+        m = (1 << fmt.depth) - 1
+        planes = {"depth": fmt.depth, "ss": fmt.ss, "samples": samples, "SSE": self.sse_tot}
+        for p, name in enumerate("YUV"):
+            planes["PSNR_" + name] = 10.0 * math.log10(m * m * samples[p] * frames / self.sse_tot[p]) if self.sse_tot[p] else None
+        for p, name in enumerate("YUV"):
+            planes["SSIM_" + name] = self.ssim_tot[p] / max(frames, 1)
+        result["planes"] = planes
+
+
+class TemporalGrader:
+    """--tc 1: `tc` is the `TemporalConsistency`, or None when the frame is too small for it: every field is null.
+    `from_output`: the flows come from the output itself (--noref 1, ctx.gt is the output), so there are no ground-truth
+    numbers.  `meta`: the "scale" and "raft" of the summary; `extra`: what follows its numbers (viz, flo_dir).  `flags`: per
+    frame, whether it was graded as a pair with the frame before it."""
+
+    def __init__(self, tab, tc, from_output, meta, extra):
+        self.tc, self.from_output, self.meta, self.extra = tc, from_output, meta, extra
+        if tc is not None:
+            self.n, self.sums = tab.ints("tc_valid", 2), tab.floats("tc_sums", 6)
+        self.flags = []
+        # valid pixels, the three sums of the output and of the ground truth, sum of (MABD - MABD_gt)^2, all over the pairs
+        self.tot = {"n": 0, "out": [0.0, 0.0, 0.0], "gt": [0.0, 0.0, 0.0], "mabd_sq": 0.0}
+
+    def launch(self, ctx, ri, rf):
+        if self.tc is not None:
+            if ctx.cut:                            # frame 0 and every scene cut: a pair never spans two sequences
+                self.tc.reset()
+            self.flags.append(self.tc.push(ctx.output, ctx.gt, ri[self.n], rf[self.sums]))
+
+    def read(self, n, rec, ri, rf):
+        rec["TC"] = None                           # the first frame of a sequence has no partner
+        if self.tc is None or not self.flags[n - 1]:
+            return
+        tot, px = self.tot, self.tc.h * self.tc.w
+        nv, o3, g3 = ri[self.n][0], rf[self.sums][0:3], None if self.from_output else rf[self.sums][3:6]
+        tot["n"] += nv
+        for q in range(3):
+            tot["out"][q] += o3[q]
+        rec["TC"] = {"N": nv, "out": o3, "gt": g3}
+        e_warp = o3[0] / (3 * nv) if nv else float("nan")
+        if g3 is None:
+            logging.info("NUM: %d, TC valid: %d, E_warp: %.6f, MABD: %.6f (flows from the output)", n, nv, e_warp, o3[2] / (3 * px))
+            return
+        for q in range(3):
+            tot["gt"][q] += g3[q]
+        tot["mabd_sq"] += (o3[2] / (3 * px) - g3[2] / (3 * px)) ** 2
+        logging.info("NUM: %d, TC valid: %d, E_warp: %.6f (gt %.6f), MABD: %.6f (gt %.6f)", n, nv, e_warp,
+                     g3[0] / (3 * nv) if nv else float("nan"), o3[2] / (3 * px), g3[2] / (3 * px))
+
+    def summary(self, result):
+        result["temporal"] = None
+        if self.tc is None:
+            return
+        tc, tot = self.tc, self.tot
+        pairs, px = sum(self.flags), tc.h * tc.w
+        te = {"scale": self.meta["scale"], "size": [tc.w, tc.h], "pairs": pairs, "raft": self.meta["raft"],
+              "valid_share": tot["n"] / (pairs * px) if pairs else None}
+        for sfx, s3 in (("", tot["out"]), ("_gt", tot["gt"])):
+            te["E_warp" + sfx] = s3[0] / (3 * tot["n"]) if tot["n"] else None
+            te["E_static" + sfx] = s3[1] / (3 * pairs * px) if pairs else None
+            te["MABD" + sfx] = s3[2] / (3 * pairs * px) if pairs else None
+        te["MABD_mse"] = tot["mabd_sq"] / pairs if pairs else None
+        if self.from_output:
+            te.update(E_warp_gt=None, E_static_gt=None, MABD_gt=None, MABD_mse=None, flow_from="output")
+        te.update(self.extra)
+        result["temporal"] = te
+        logging.info("temporal (scale %d, %d pairs): %s", te["scale"], pairs,
+                     ", ".join("%s: %s" % (k, "null" if te[k] is None else "%.6g" % te[k]) for k in
+                               ("valid_share", "E_warp", "E_warp_gt", "E_static", "E_static_gt", "MABD", "MABD_gt", "MABD_mse")))
+
+
+class TemporalPictures:
+    """--tc_viz / --tc_flo_dir, after the temporal grader's launch: `viz` = (Y4MWriter, its format, radius, gain):
+    one picture per frame, of the pair or of the frame alone, rendered in float and encoded by the kernel of the enhance stream;
+    `flo` = (FloWriter, directory): the two flows of every graded pair.  Either may be None."""
+
+    def __init__(self, ops, tc, dev, viz, flo):
+        self.ops, self.tc, self.viz, self.flo = ops, tc, viz, flo
+        if viz is not None:
+            self.rgb = torch.empty((1, 3, 2 * tc.h, 2 * tc.w), dtype=torch.float32, device=dev)
+            self.yuv = torch.empty(viz[1].frame_bytes, dtype=torch.uint8, device=dev)
+
+    def submit(self, frame, paired):
+        ops, tc = self.ops, self.tc
+        if self.viz is not None:
+            writer, fmt, radius, gain = self.viz
+            tc.viz(self.rgb, "out", radius, gain)
+            writer.submit(ops.rgb_f32_to_yuv(self.rgb, fmt, out=self.yuv))
+        if self.flo is not None and paired:
+            for flow, name in ((tc.fb, "bwd"), (tc.ff, "fwd")):
+                self.flo[0].submit(os.path.join(self.flo[1], "%06d_%s.flo" % (frame, name)), ops.flow_pack(flow, tc.h, tc.w))
+
+
+def loe50_grid(H, W):
+    """the sample grid of LOE_50: the short side becomes 50, the other side keeps the aspect, each rounded half up"""
+    m = min(H, W)
+    return (100 * H + m) // (2 * m), (100 * W + m) // (2 * m)
+
+
+def noref_values(full, ents, sub):
+    """the per-frame numbers of --noref 1 from what `Ops.noref` returns on the full grid (six integers `full`, two entropies
+    `ents`) and on the LOE_50 grid (`sub`): [Ns, S_loe, S_a, S_b, n_sat, n_black]"""
+    ns = full[0]
+    l_in, l_out = full[2] / ns, full[3] / ns
+    return {"LOE": full[1] / (ns * (ns - 1)) if ns > 1 else None, "LOE_50": sub[1] / sub[0], "L_in": l_in, "L_out": l_out,
+            "gain": l_out / l_in if full[2] else None, "entropy_in": ents[0], "entropy_out": ents[1], "sat_out": full[4] / ns,
+            "black_out": full[5] / ns}
+
+
+class NorefGrader:
+    """--noref 1: `Ops.noref` of the decoded input as the network saw it (step.x) against the output, on the full
+    grid and on the LOE_50 grid `grid50`"""
+
+    def __init__(self, tab, ops, grid50):
+        self.ops, self.grid50 = ops, grid50
+        self.full, self.ents = tab.ints("noref", 6), tab.floats("noref_entropy", 2)
+        self.sub, self.ents_sub = tab.ints("noref_50", 6), tab.floats("noref_50_entropy", 2)     # its entropies are not reported
+        # per key the sum of the frames' values and the number of frames that have one; sum of S_a and of S_b
+        self.tot, self.count, self.s = dict.fromkeys(NR_KEYS, 0.0), dict.fromkeys(NR_KEYS, 0), [0, 0]
+
+    def launch(self, ctx, ri, rf):
+        self.ops.noref(ctx.step.x, ctx.output, out_i=ri[self.full], out_f=rf[self.ents])
+        self.ops.noref(ctx.step.x, ctx.output, grid=self.grid50, out_i=ri[self.sub], out_f=rf[self.ents_sub])
+
+    def read(self, n, rec, ri, rf):
+        tot, count, s = self.tot, self.count, self.s
+        full, sub = ri[self.full], ri[self.sub]
+        v = noref_values(full, rf[self.ents], sub)
+        for key in NR_KEYS:
+            if v[key] is not None:
+                tot[key] += v[key]
+                count[key] += 1
+        s[0] += full[2]
+        s[1] += full[3]
+        rec["noref"] = dict(v, ints=full, ints_50=sub)
+        logging.info("NUM: %d, " + ", ".join(key + ": %s" for key in NR_KEYS), n,
+                     *["null" if v[key] is None else "%.4f" % v[key] for key in NR_KEYS])
+        logging.info("Total LOE: %s, Total LOE_50: %.4f, Total L_out: %.4f, Total gain: %s",
+                     "%.4f" % (tot["LOE"] / count["LOE"]) if count["LOE"] else "null", tot["LOE_50"] / n, tot["L_out"] / n,
+                     "%.4f" % (s[1] / s[0]) if s[0] else "null")
+
+    def summary(self, result):
+        nr = dict({"graded": "denoise"}, **{k: self.tot[k] / self.count[k] if self.count[k] else None for k in NR_KEYS})
+        nr["gain"] = self.s[1] / self.s[0] if self.s[0] else None               # of the stream: sum S_b / sum S_a
+        result["noref"] = nr
+        logging.info("no-reference (%d frames, the denoise result against the decoded input): %s", result["images"],
+                     ", ".join("%s: %s" % (k, "null" if nr[k] is None else "%.6g" % nr[k]) for k in NR_KEYS))
