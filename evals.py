@@ -28,6 +28,7 @@ grading = importlib.import_module("zero-tig_amd.grading")
 scenecut = importlib.import_module("zero-tig_amd.scenecut")
 videorun = importlib.import_module("zero-tig_amd.videorun")
 loe50_grid, noref_values, NR_KEYS = grading.loe50_grid, grading.noref_values, grading.NR_KEYS
+color_values, COLOR_KEYS = grading.color_values, grading.COLOR_KEYS
 
 parser =argparse.ArgumentParser("ZERO-IG")
 parser.add_argument("--lowlight_images_path", type=str, default="./lowlight_dataset")
@@ -89,6 +90,14 @@ parser.add_argument("--noref", type=int, default=0, choices=[0, 1],
                          "lightness of both and its gain, the entropies of the two lightness histograms and the saturated / black shares "
                          "of the result, under \"noref\" in Metrics.json; takes no --y4m_gt; with --tc 1 the flows come from RAFT on the "
                          "denoise result itself; needs --y4m_in")
+parser.add_argument("--color", type=int, default=0, choices=[0, 1],
+                    help="1: no-reference colour measures (DESIGN 8m), under \"color\" in Metrics.json: UIQM with its parts UICM / UISM / "
+                         "UIConM (Panetta et al. 2016), UCIQE with its parts (Yang and Sowmya 2015), Hasler-Suesstrunk colourfulness and "
+                         "the mean RGB level; with --y4m_in of the denoise result (\"out\"), of the decoded input (\"in\") and, with "
+                         "--y4m_gt, of the ground truth (\"gt\"); in dataset mode of the result and the ground truth of each pair")
+parser.add_argument("--color_block", type=int, default=None,
+                    help="the side B of the blocks of UISM and UIConM, 4..64; default 10; the rows and columns beyond the last whole "
+                         "block are in no block; needs --color 1")
 parser.add_argument("--tc_scale", type=int, default=None,
                     help="integer S >= 1: the temporal metrics are taken at (H // S, W // S); default --of_scale; needs --tc 1")
 parser.add_argument("--tc_raft_weights", type=str, default=None,
@@ -119,6 +128,12 @@ CHUNK = 64                                         # frames per read-back of the
 
 def check_y4m_args(args):
     """every argument check of the video mode, before anything touches the device -> True when the video mode was asked for"""
+    if args.color_block is not None and not args.color:
+        parser.error("--color_block needs --color 1")
+    if args.color:
+        args.color_block = 10 if args.color_block is None else args.color_block
+        if not 4 <= args.color_block <= 64:
+            parser.error("--color_block is the side of a block in pixels, 4..64; got %d" % args.color_block)
     explicit_hm = args.hist_match is not None
     if not explicit_hm:
         args.hist_match = 0 if args.noref else 1
@@ -334,6 +349,8 @@ def main_y4m(args):
             tc_meta = {"scale": args.tc_scale, "raft": "file" if args.tc_raft_weights else "checkpoint"}
             temporal_grader = grading.TemporalGrader(tab, tc, noref, tc_meta, tc_extra)
             graders.append(temporal_grader)
+        if args.color:
+            graders.append(grading.ColorGrader(tab, ops, args.color_block, ("out", "in") + (() if noref else ("gt",))))
         tab.build()
         ctx = types.SimpleNamespace(step=step, output=None, gt=None, gt_yuv=None if noref else gt.payload, cut=False)
         records, frames, t_first = [], 0, None
@@ -395,6 +412,8 @@ def main_y4m(args):
         result["cuts"] = seq.cuts
     if args.tc:
         result["temporal"] = None
+    if args.color:
+        result["color"] = None
     for g in graders:
         g.summary(result)
     with open(os.path.join(args.save, "Metrics.json"), "w") as fh:
@@ -413,6 +432,7 @@ def main_y4m(args):
         with open(args.timing_json, "w") as fh:
             json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), graph=args.graph, y4m=1,
                            hist_match=int(hm_on), lpips=int(lp_on), planes=int(plane_fmt is not None), **({"noref": 1} if noref else {}),
+                           **({"color": 1} if args.color else {}),
                            scene_wait_ms=1e3 * det.wait / frames if det is not None else None,
                            **({"tc": int(tc is not None), "tc_scale": args.tc_scale} if args.tc else {})), fh)
     logging.info("Total frame number: %d", frames)
@@ -443,6 +463,7 @@ def main():
     total_ssim, total_hm, total_ssim_hm = 0.0, 0.0, 0.0
     lpips_model = utils.lpips_model(args.lpips_weights, dev, args.lpips_precision) if args.lpips_weights else None
     total_lpips, total_lpips_hm = 0.0, 0.0
+    color_means, color_blocks = {"out": grading.ColorMeans(), "gt": grading.ColorMeans()}, None
     step = None
     if args.graph:
         import importlib
@@ -485,6 +506,12 @@ def main():
                     logging.info("NUM: %d, PSNR_HM: %.3f, SSIM_HM: %.3f, LPIPS_HM: %.3f", n, psnr_hm, ssim_hm, lp_hm)
                     logging.info("Total PSNR_HM: %.3f, Total SSIM_HM: %.3f, Total LPIPS_HM: %.3f", total_hm / n, total_ssim_hm / n,
                                  total_lpips_hm / n)
+            if args.color:                                         # read back per image, as PSNR is
+                color_blocks = [output.shape[2] // args.color_block, output.shape[3] // args.color_block]
+                for which, frame in (("out", output), ("gt", gt_t)):
+                    v = utils.color_quality(frame, args.color_block)
+                    color_means[which].add(v)
+                    logging.info("NUM: %d, color %s: %s", n, which, grading.color_text(v))
             if i < args.save_images:
                 parts = img_path[0].split(os.sep)
                 save_dir = os.path.join(args.save, parts[-3] + "/" + parts[-2])
@@ -504,10 +531,16 @@ def main():
     with open(os.path.join(args.save, "Metrics.json"), "w") as fh:
         hm_on = bool(args.hist_match)
         lp_on = lpips_model is not None
-        json.dump({"Total_PSNR": total / max(n, 1), "Total_SSIM": total_ssim / max(n, 1),
-                   "Total_LPIPS": total_lpips / max(n, 1) if lp_on else None,
-                   "Total_PSNR_HM": total_hm / max(n, 1) if hm_on else None, "Total_SSIM_HM": total_ssim_hm / max(n, 1) if hm_on else None,
-                   "Total_LPIPS_HM": total_lpips_hm / max(n, 1) if lp_on and hm_on else None, "images": n}, fh)
+        result = {"Total_PSNR": total / max(n, 1), "Total_SSIM": total_ssim / max(n, 1),
+                  "Total_LPIPS": total_lpips / max(n, 1) if lp_on else None,
+                  "Total_PSNR_HM": total_hm / max(n, 1) if hm_on else None, "Total_SSIM_HM": total_ssim_hm / max(n, 1) if hm_on else None,
+                  "Total_LPIPS_HM": total_lpips_hm / max(n, 1) if lp_on and hm_on else None, "images": n}
+        if args.color:
+            result["color"] = {"block": args.color_block, "graded": "denoise", "blocks": color_blocks, "out": color_means["out"].means(),
+                               "in": None, "gt": color_means["gt"].means()}
+            logging.info("colour (%d images, blocks of %d): out %s; gt %s", n, args.color_block,
+                         grading.color_text(result["color"]["out"]), grading.color_text(result["color"]["gt"]))
+        json.dump(result, fh)
 
 
 if __name__ == "__main__":

@@ -489,6 +489,34 @@ int zt_flow_pack_hwc_f32(const float* flow, int H, int W, int Hf, int Wf, int oy
 int zt_lightness_joint_hist_f32(const float* a, const float* b, int H, int W, int Hs, int Ws, unsigned int* hist, zt_stream_t stream);
 int zt_noref_from_hist(const unsigned int* hist, long long* out_i /* [6] */, double* out_f /* [2] */, zt_stream_t stream);
 
+/* ---- no-reference colour grading of a frame (zt_color.hip): evals.py --color 1, DESIGN 8m --------------------------------------------
+ * x: planar fp32 [3][H][W].  Levels R, G, B = zt_quant_u8(v, 1) = rint(v * 255) & 255; N = H * W; block = B, 4..64; k1 = W / B,
+ * k2 = H / B, nblk = k1 * k2; block (i, j) is rows iB .. iB + B - 1, columns jB .. jB + B - 1, the rows and columns left over are in
+ * no block.  lin16: uint32 [256], the sRGB decoding of a level times 65535, rounded; flut: fp32 [65536], the CIELAB f(i / 65535); both
+ * are made by the caller in fp64 (zero-tig_amd/ops.py).  Per pixel, in unsigned 32-bit and then in fp32 with one rounding an operation:
+ *     r, g, b = lin16[R], lin16[G], lin16[B]
+ *     X16 = (28440 r + 24655 g + 12441 b + 32768) >> 16, Y16 = (13938 r + 46868 g + 4730 b + 32768) >> 16,
+ *     Z16 = (1164 r + 7174 g + 57198 b + 32768) >> 16;  fx, fy, fz = flut[X16], flut[Y16], flut[Z16]
+ *     L = 116 fy - 16; a = 500 (fx - fy); b = 200 (fy - fz); C = sqrtf(a a + b b); D = sqrtf(C C + L L); S = D > 0 ? C / D : 0
+ *     kL = (int)floorf(L * 10) clamped to 0..1000
+ * Per channel c and pixel of a block, e2 = (gx gx + gy gy) c c with the 3 x 3 Sobel pair on the levels, frame borders replicated
+ * (a block's rim reads the real pixels beyond it); per block and channel emax2 / emin2 = the largest / smallest e2, and cmax / cmin
+ * = the largest / smallest of the block's 3 B B levels.
+ * out_i = { N, nblk, sum R, sum G, sum B, S1 S2 T of R - G, S1 S2 T of R + G - 2B, n_kept, k01, k99, the number of blocks with
+ *   emin2 == 0 for R, G, B, the number of blocks with cmax == cmin }: S1 / S2 the sum / the sum of squares; T the sum of the values
+ *   that are left when, in ascending order, the first TL = (N + 9) / 10 and the last TR = N / 10 are dropped, n_kept = N - TL - TR;
+ *   k01 / k99 the smallest kL whose cumulative count reaches (N + 99) / 100 / (99 N + 99) / 100.  Exact 64-bit integers.
+ * out_f = { sum C, sum (double)C (double)C, sum S, E_R, E_G, E_B, A }: E_c = sum over the blocks with emin2 > 0 of
+ *   log(emax2 / emin2), A = sum over the blocks with cmax > cmin of r log(r), r = (cmax - cmin) / (cmax + cmin), in fp64.
+ * One pass over the frame by at most max_workgroups workgroups (0: the default, 256; at most 1024), each with a private table of the
+ * six histograms in LDS that it adds to the table in ws with integer atomics, and its own fp64 sums; then one workgroup finishes.  The order of every fp64
+ * sum follows from H, W, block and max_workgroups alone: the same call gives the same bits.  ws: 8-byte aligned, at least the size
+ * zt_color_ws_bytes reports (a pure host query); nothing in it is kept between calls.  H, W < 1, H * W >= 2^31, block outside
+ * 4..64, max_workgroups < 0, a NULL or misaligned pointer, a workspace too small: ZT_EINVAL.  Nothing synchronises. */
+int zt_color_ws_bytes(int H, int W, int block, size_t* bytes);
+int zt_color_stats_f32(const float* x, int H, int W, int block, const unsigned int* lin16, const float* flut, int max_workgroups,
+                       void* ws, size_t ws_bytes, long long* out_i /* [18] */, double* out_f /* [7] */, zt_stream_t stream);
+
 /* ---- result PNGs encoded on the device (zt_png.hip) ------------------------------------------------------------------
  * predict.py:57-61, 101-104 (and evals.py's --save_images files): `Image.fromarray(u8).save(path, "PNG")`.  src: uint8 [H][W][3] (what
  * zt_quantize_u8_hwc writes) -> out: a complete zlib stream (78 01, deflate blocks, big-endian Adler-32) of the Paeth-filtered

@@ -29,6 +29,11 @@
     evals_tcviz_pic evals_tcviz --skip-kernels --skip-temporal --frames 128 --out profiles/evals_tcviz_1080p.json` is the run behind
     that file.
 
+(f) colour: `evals_color` = `evals_noref` with --color 1 in part (b), and `Ops.color_stats` alone at 1080p on four
+    inputs (the low-light frame, its clean twin, a constant frame, uniform noise), at the default grid and at three others, with
+    blocks of 10, 8 and 64, next to `Ops.ssim_u8_dev` in the same process.  `--settings evals_noref evals_color --skip-kernels
+    --skip-temporal --frames 128 --out profiles/color_1080p.json` is the run behind that file.
+
 This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
 ends the run.  Writes the JSON to --out and prints it as one line.
 Usage: python tools/bench_evals_y4m.py [--frames 256] [--out profiles/evals_y4m_1080p.json]"""
@@ -221,6 +226,58 @@ def noref_mode(a):
         json.dump(out, fh)
 
 
+# ---- child: zt_color_stats_f32 alone, next to zt_ssim_u8_f32 ----------------------------------------------------------------
+def color_mode(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("zero-tig_amd.lib").get_lib()               # raises without a HIP device
+    ops = importlib.import_module("zero-tig_amd.ops").Ops(lib)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    grading = importlib.import_module("zero-tig_amd.grading")
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+
+    def dev_frame(x):
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(1, 3, H, W))).to(dev)
+
+    def timed(fn):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return {"ms": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
+    inputs = {"synth_lowlight": dev_frame(synth.lowlight_frame(3, H, W)), "synth_clean": dev_frame(synth.clean_frame(3, H, W)),
+              "constant": torch.full((1, 3, H, W), 0.25, device=dev), "uniform_noise": dev_frame(rng.random((3, H, W), dtype=np.float32))}
+    out = {"what": "HIP-event median of %d calls at 1080 x 1920: color = Ops.color_stats, blocks of 10 (the memset of the table, the "
+                   "pass over the frame and the finishing workgroup; it reads the frame once, bytes = 12 H W), color_wgN = the same "
+                   "with max_workgroups = N (the default grid is 216 workgroups here, one unit each), color_b8 / color_b64 = blocks of 8 / 64, "
+                   "ssim_u8 = Ops.ssim_u8_dev of the frame against the clean frame, in the same process" % a.reps}
+    for name, x in inputs.items():
+        oi, of = torch.empty(18, dtype=torch.int64, device=dev), torch.empty(7, dtype=torch.float64, device=dev)
+        one = torch.empty(1, dtype=torch.float64, device=dev)
+        row = {"color": timed(lambda: ops.color_stats(x, 10, out_i=oi, out_f=of))}
+        row["color"].update(bytes=12 * H * W, gbs=round(12 * H * W / row["color"]["ms"] / 1e6, 1))
+        for wg in (27, 54, 108):
+            row["color_wg%d" % wg] = timed(lambda: ops.color_stats(x, 10, out_i=oi, out_f=of, max_workgroups=wg))
+        for b in (8, 64):
+            row["color_b%d" % b] = timed(lambda: ops.color_stats(x, b, out_i=oi, out_f=of))
+        row["ssim_u8"] = timed(lambda: ops.ssim_u8_dev(x, inputs["synth_clean"], out=one))
+        ops.color_stats(x, 10, out_i=oi, out_f=of)
+        row.update(ints=oi.tolist(), sums=of.tolist(), values=grading.color_values(oi.tolist(), of.tolist(), 10))
+        out[name] = row
+        print("[bench_evals_y4m] color %s %s" % (name, row), file=sys.stderr, flush=True)
+    with open(a.json, "w") as fh:
+        json.dump(out, fh)
+
+
 # ---- child: the kernels of zt_flowviz.hip alone at the reduced size of --tc_scale 3 --------------------------------------
 def tcviz_mode(a):
     import numpy as np
@@ -335,7 +392,7 @@ def gpu_step(cmd, limit, env=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels", "temporal", "noref", "tcviz"])
+    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels", "temporal", "noref", "tcviz", "color"])
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--frames", type=int, default=256)
@@ -343,7 +400,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--settings", type=str, nargs="*", default=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1"],
                     choices=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1", "evals_noref", "evals_tcviz_pic",
-                             "evals_tcviz"])
+                             "evals_tcviz", "evals_color"])
     ap.add_argument("--skip-kernels", action="store_true", help="part (b) only")
     ap.add_argument("--skip-temporal", action="store_true", help="without the temporal kernel's own timing (part (c))")
     ap.add_argument("--step-timeout", type=int, default=240)
@@ -357,6 +414,8 @@ def main():
         return noref_mode(a)
     if a.mode == "tcviz":
         return tcviz_mode(a)
+    if a.mode == "color":
+        return color_mode(a)
     out = {"what": "evals.py --y4m_in / --y4m_gt next to predict.py --y4m_in, --graph 1 --precision bf16, over one synthetic 1080p "
                    "C420mpeg2 pair of %d frames (%d distinct), %d runs per setting, the runs alternating, one session on one box; fps "
                    "and the host-side split per frame from each script's --timing_json (predict: first frame read to last stream "
@@ -366,7 +425,9 @@ def main():
                    "of %d calls; evals_tc3 / evals_tc1 = evals with --tc 1 at --tc_scale 3 / 1; temporal_kernels = Ops.warp_error, "
                    "Ops.warp2 and one RAFT run of TemporalConsistency alone; evals_noref = --noref 1, no ground truth (DESIGN 8j); "
                    "noref_kernels = the two entry points of zt_noref.hip alone; evals_tcviz / evals_tcviz_pic = evals_tc3 with --tc_viz and "
-                   "--tc_flo_dir / with --tc_viz alone (DESIGN 8k), tcviz_kernels = the kernels of zt_flowviz.hip alone" % (a.frames, a.distinct, a.repeats, a.reps),
+                   "--tc_flo_dir / with --tc_viz alone (DESIGN 8k), tcviz_kernels = the kernels of zt_flowviz.hip alone; evals_color = "
+                   "--noref 1 --color 1 (DESIGN 8m), the yardstick is evals_noref in the same run, color_kernels = zt_color_stats_f32 "
+                   "alone" % (a.frames, a.distinct, a.repeats, a.reps),
             "cpus": len(os.sched_getaffinity(0))}
     tmp = tempfile.mkdtemp(prefix="zt_bench_evals_y4m_")
     try:
@@ -386,6 +447,10 @@ def main():
             kj = os.path.join(tmp, "tcviz.json")
             gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "tcviz", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
             out["tcviz_kernels"] = json.load(open(kj))
+        if "evals_color" in a.settings:
+            kj = os.path.join(tmp, "color.json")
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "color", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
+            out["color_kernels"] = json.load(open(kj))
         files = make_pair(tmp, a.frames, a.distinct)
         viz, flo = os.path.join(tmp, "viz.y4m"), os.path.join(tmp, "flo")
         env = dict(os.environ, PYTHONPATH=ROOT)
@@ -395,6 +460,7 @@ def main():
                  "evals_tc3": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "3"],
                  "evals_tc1": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "1"],
                  "evals_noref": ["--noref", "1"]}
+        extra["evals_color"] = extra["evals_noref"] + ["--color", "1"]
         extra["evals_tcviz_pic"] = extra["evals_tc3"] + ["--tc_viz", viz]
         extra["evals_tcviz"] = extra["evals_tcviz_pic"] + ["--tc_flo_dir", flo]
         loops, wall, written = {s: [] for s in a.settings}, {s: [] for s in a.settings}, {}
@@ -432,6 +498,10 @@ def main():
             for s in a.settings:
                 if s.startswith("evals_tcviz"):
                     out["end_to_end"][s]["tcviz_over_tc3_ms_per_frame"] = round(out["end_to_end"][s]["ms_per_frame_median"] - base, 3)
+        if "evals_noref" in a.settings and "evals_color" in a.settings:
+            e2e = out["end_to_end"]
+            e2e["evals_color"]["color_over_noref_ms_per_frame"] = round(e2e["evals_color"]["ms_per_frame_median"] -
+                                                                        e2e["evals_noref"]["ms_per_frame_median"], 3)
         if "predict" in a.settings:
             base = out["end_to_end"]["predict"]["ms_per_frame_median"]
             for s in a.settings:

@@ -161,6 +161,15 @@ def histogram_match(out, gt):
     return _ops().match_histograms(_prep(out), _prep(gt))
 
 
+def color_quality(img, block=10):
+    """the no-reference colour measures of a [1,3,H,W] frame in [0,1] on the device -> dict: UIQM and its parts UICM,
+    UISM, UIConM (blocks of `block` x `block` pixels), UCIQE and its parts sigma_c, con_l, mu_s, colorfulness, mean_rgb; None where
+    a measure has no value (a frame smaller than a block); synchronous: the 18 integers and the 7 sums are read back."""
+    oi, of = _ops().color_stats(_prep(img), block)
+    grading = importlib.import_module("zero-tig_amd.grading")
+    return grading.color_values(oi.tolist(), of.tolist(), block)
+
+
 def lpips_model(path, device, precision="fp32"):
     """evals.py:73-80 `lpips.LPIPS(net='vgg')` on the device from the user's weights file (`torch.save(lpips.LPIPS(net='vgg')
     .state_dict(), path)`; torchvision's `features.<idx>.*` names are accepted for the convs).  precision: "fp32" or "bf16"."""

@@ -14,6 +14,7 @@ import types
 import torch
 
 NR_KEYS = ("LOE", "LOE_50", "L_in", "L_out", "gain", "entropy_in", "entropy_out", "sat_out", "black_out")
+COLOR_KEYS = ("UIQM", "UICM", "UISM", "UIConM", "UCIQE", "sigma_c", "con_l", "mu_s", "colorfulness", "mean_rgb")
 
 
 class MetricTable:
@@ -273,6 +274,98 @@ def noref_values(full, ents, sub):
     return {"LOE": full[1] / (ns * (ns - 1)) if ns > 1 else None, "LOE_50": sub[1] / sub[0], "L_in": l_in, "L_out": l_out,
             "gain": l_out / l_in if full[2] else None, "entropy_in": ents[0], "entropy_out": ents[1], "sat_out": full[4] / ns,
             "black_out": full[5] / ns}
+
+
+def color_values(ints, floats, block):
+    """the colour measures of a frame from what `Ops.color_stats` returns for blocks of `block` pixels, 18 integers and
+    7 floats as include/zerotig_hip.h lists them; float64; None where a denominator is 0 (one pixel: nothing is left after the
+    trimming; a frame smaller than a block)"""
+    n, nblk = ints[0], ints[1]
+    assert n >= 1 and 0 <= nblk * block * block <= n, (n, nblk, block)
+    s1_rg, s2_rg, t_rg, s1_yb, s2_yb, t_yb, kept, k01, k99 = ints[5:14]
+    sum_c, sum_c2, sum_s, e_r, e_g, e_b, a = floats
+    uicm = None
+    if kept:                                       # the spread of all the pixels about the trimmed mean, as in the paper
+        mu_rg, mu_yb = t_rg / kept, t_yb / (2 * kept)
+        var_rg = s2_rg / n - 2.0 * mu_rg * s1_rg / n + mu_rg * mu_rg
+        var_yb = s2_yb / (4 * n) - 2.0 * mu_yb * s1_yb / (2 * n) + mu_yb * mu_yb
+        uicm = -0.0268 * math.hypot(mu_rg, mu_yb) + 0.1586 * math.sqrt(max(var_rg + var_yb, 0.0))
+    uism = (0.299 * e_r + 0.587 * e_g + 0.114 * e_b) / nblk if nblk else None
+    uiconm = -a / nblk if nblk else None
+    uiqm = None if uicm is None or uism is None else 0.0282 * uicm + 0.2953 * uism + 3.5753 * uiconm
+    sigma_c = math.sqrt(max(sum_c2 / n - (sum_c / n) ** 2, 0.0)) / 255.0
+    con_l, mu_s = (k99 - k01) / 1000.0, sum_s / n
+    m_rg, m_yb = s1_rg / n, s1_yb / (2 * n)       # Hasler and Suesstrunk: the plain means and variances
+    v_rg, v_yb = s2_rg / n - m_rg * m_rg, s2_yb / (4 * n) - m_yb * m_yb
+    return {"UIQM": uiqm, "UICM": uicm, "UISM": uism, "UIConM": uiconm,
+            "UCIQE": 0.4680 * sigma_c + 0.2745 * con_l + 0.2576 * mu_s, "sigma_c": sigma_c, "con_l": con_l, "mu_s": mu_s,
+            "colorfulness": math.sqrt(max(v_rg + v_yb, 0.0)) + 0.3 * math.hypot(m_rg, m_yb), "mean_rgb": [s / n for s in ints[2:5]]}
+
+
+class ColorMeans:
+    """per key of COLOR_KEYS the sum of the frames' values and the number of frames that have one (`NorefGrader`'s rule)"""
+
+    def __init__(self):
+        self.tot = dict.fromkeys(COLOR_KEYS, 0.0)
+        self.tot["mean_rgb"] = [0.0, 0.0, 0.0]
+        self.count = dict.fromkeys(COLOR_KEYS, 0)
+
+    def add(self, v):
+        for key in COLOR_KEYS:
+            if v[key] is None:
+                continue
+            if key == "mean_rgb":
+                self.tot[key] = [t + x for t, x in zip(self.tot[key], v[key])]
+            else:
+                self.tot[key] += v[key]
+            self.count[key] += 1
+
+    def means(self):
+        out = {}
+        for key in COLOR_KEYS:
+            c, t = self.count[key], self.tot[key]
+            out[key] = None if not c else [x / c for x in t] if key == "mean_rgb" else t / c
+        return out
+
+
+def color_text(v):
+    return ", ".join("%s: %s" % (k, "null" if v[k] is None else "%.4f" % v[k]) for k in ("UIQM", "UICM", "UISM", "UIConM", "UCIQE",
+                                                                                       "colorfulness"))
+
+
+class ColorGrader:
+    """--color 1: one `Ops.color_stats` with blocks of `block` pixels per graded frame; `which` names the frames, in
+    the order of the log: "out" the denoise result, "in" the decoded input as the network saw it (step.x), "gt" the ground truth"""
+
+    def __init__(self, tab, ops, block, which):
+        self.ops, self.block, self.which = ops, block, tuple(which)
+        self.cols = {w: (tab.ints("color_" + w, 18), tab.floats("color_" + w + "_sums", 7)) for w in self.which}
+        self.means = {w: ColorMeans() for w in self.which}
+        self.blocks = None                         # [k2, k1] of the frames, known from the first one
+
+    def launch(self, ctx, ri, rf):
+        frames = {"out": ctx.output, "in": ctx.step.x, "gt": ctx.gt}
+        if self.blocks is None:
+            self.blocks = [int(ctx.output.shape[2]) // self.block, int(ctx.output.shape[3]) // self.block]
+        for w in self.which:
+            ci, cf = self.cols[w]
+            self.ops.color_stats(frames[w], self.block, out_i=ri[ci], out_f=rf[cf])
+
+    def read(self, n, rec, ri, rf):
+        rec["color"] = {}
+        for w in self.which:
+            ci, cf = self.cols[w]
+            v = color_values(ri[ci], rf[cf], self.block)
+            self.means[w].add(v)
+            rec["color"][w] = dict(v, ints=ri[ci], sums=rf[cf])
+            logging.info("NUM: %d, color %s: %s", n, w, color_text(v))
+
+    def summary(self, result):
+        co = {"block": self.block, "graded": "denoise", "blocks": self.blocks, "out": None, "in": None, "gt": None}
+        co.update({w: self.means[w].means() for w in self.which})
+        result["color"] = co
+        logging.info("colour (%d frames, blocks of %d): %s", result["images"], self.block,
+                     "; ".join("%s %s" % (w, color_text(co[w])) for w in self.which))
 
 
 class NorefGrader:

@@ -681,6 +681,44 @@ class Ops:
         self.lib.call("zt_noref_from_hist", hist, out_i, out_f, self._s(a))
         return out_i, out_f
 
+    # ---- no-reference colour grading of a frame (zt_color.hip) --------------------------------------------
+    def color_stats(self, x, block=10, out_i=None, out_f=None, max_workgroups=0):
+        """the raw numbers of UIQM, UCIQE and colourfulness of the fp32 [1,3,H,W] frame `x` with blocks of `block` x `block` pixels
+        (4..64) -> (int64 [18], float64 [7]) on the device, as include/zerotig_hip.h lists them; `grading.color_values` turns them
+        into the measures.  Nothing synchronises; `out_i` / `out_f` (e.g. cells of a table row) are overwritten.  `max_workgroups`
+        caps the grid of the pass over the frame (0: the default).  The two CIELAB tables, made here in float64, and the
+        workspace are cached per device."""
+        import ctypes
+        import numpy as np
+        _f32c(x)
+        assert x.dim() == 4 and x.shape[0] == 1 and x.shape[1] == 3, tuple(x.shape)
+        H, W = int(x.shape[2]), int(x.shape[3])
+        assert H >= 1 and W >= 1 and H * W < 1 << 31, (H, W)
+        assert int(block) == block and 4 <= block <= 64, block
+        assert int(max_workgroups) == max_workgroups and max_workgroups >= 0, max_workgroups
+        dev = x.device
+        cache = self.__dict__.setdefault("_color_cache", {})
+        c = cache.get(str(dev))
+        if c is None:
+            v = np.arange(256, dtype=np.float64) / 255.0
+            lin16 = np.rint(65535.0 * np.where(v <= 0.04045, v / 12.92, ((v + 0.055) / 1.055) ** 2.4)).astype(np.int32)
+            t = np.arange(65536, dtype=np.float64) / 65535.0
+            flut = np.where(t > 216.0 / 24389.0, np.cbrt(t), (24389.0 / 27.0 * t + 16.0) / 116.0).astype(np.float32)
+            c = cache[str(dev)] = {"lin16": torch.from_numpy(lin16).to(dev), "flut": torch.from_numpy(flut).to(dev), "ws": None}
+        need = ctypes.c_size_t(0)
+        self.lib.call("zt_color_ws_bytes", H, W, int(block), ctypes.byref(need))
+        if c["ws"] is None or c["ws"].numel() * 8 < need.value:
+            c["ws"] = torch.empty((need.value + 7) // 8, dtype=torch.int64, device=dev)
+        if out_i is None:
+            out_i = torch.empty(18, dtype=torch.int64, device=dev)
+        if out_f is None:
+            out_f = torch.empty(7, dtype=torch.float64, device=dev)
+        assert tuple(out_i.shape) == (18,) and out_i.dtype == torch.int64 and out_i.is_contiguous() and out_i.device == dev
+        assert tuple(out_f.shape) == (7,) and out_f.dtype == torch.float64 and out_f.is_contiguous() and out_f.device == dev
+        self.lib.call("zt_color_stats_f32", x, H, W, int(block), c["lin16"], c["flut"], int(max_workgroups), c["ws"],
+                      c["ws"].numel() * 8, out_i, out_f, self._s(x))
+        return out_i, out_f
+
     def psnr_u8(self, a, b):
         """evals.py:83-85: cv2.PSNR of round(a*255), round(b*255) -> python float (inf when identical); one 8-byte read-back."""
         _f32c(a), _f32c(b)
