@@ -98,6 +98,12 @@ parser.add_argument("--color", type=int, default=0, choices=[0, 1],
 parser.add_argument("--color_block", type=int, default=None,
                     help="the side B of the blocks of UISM and UIConM, 4..64; default 10; the rows and columns beyond the last whole "
                          "block are in no block; needs --color 1")
+parser.add_argument("--niqe", type=str, default=None,
+                    help="MODEL.npz: NIQE (Mittal et al. 2013; DESIGN 8n), under \"niqe\" in Metrics.json, against the pristine model in "
+                         "the file (mu_pris_param [36], cov_pris_param [36,36], as the Python ports keep it and as tools/niqe_fit.py "
+                         "writes it from footage of your own; the MATLAB release's .mat with scipy): with --y4m_in of the denoise result "
+                         "(\"out\"), of the decoded input (\"in\") and, with --y4m_gt, of the ground truth (\"gt\"); in dataset mode of "
+                         "the result and the ground truth of each pair; frames with fewer than two whole 96 x 96 blocks give null")
 parser.add_argument("--tc_scale", type=int, default=None,
                     help="integer S >= 1: the temporal metrics are taken at (H // S, W // S); default --of_scale; needs --tc 1")
 parser.add_argument("--tc_raft_weights", type=str, default=None,
@@ -134,6 +140,9 @@ def check_y4m_args(args):
         args.color_block = 10 if args.color_block is None else args.color_block
         if not 4 <= args.color_block <= 64:
             parser.error("--color_block is the side of a block in pixels, 4..64; got %d" % args.color_block)
+    if args.niqe is not None and not os.path.isfile(args.niqe):
+        parser.error("--niqe %s: no such file (a pristine model, .npz with mu_pris_param and cov_pris_param; tools/niqe_fit.py "
+                     "fits one)" % args.niqe)
     explicit_hm = args.hist_match is not None
     if not explicit_hm:
         args.hist_match = 0 if args.noref else 1
@@ -351,6 +360,8 @@ def main_y4m(args):
             graders.append(temporal_grader)
         if args.color:
             graders.append(grading.ColorGrader(tab, ops, args.color_block, ("out", "in") + (() if noref else ("gt",))))
+        if args.niqe:
+            graders.append(grading.NiqeGrader(tab, ops, grading.NiqeModel.load(args.niqe), ("out", "in") + (() if noref else ("gt",))))
         tab.build()
         ctx = types.SimpleNamespace(step=step, output=None, gt=None, gt_yuv=None if noref else gt.payload, cut=False)
         records, frames, t_first = [], 0, None
@@ -414,6 +425,8 @@ def main_y4m(args):
         result["temporal"] = None
     if args.color:
         result["color"] = None
+    if args.niqe:
+        result["niqe"] = None
     for g in graders:
         g.summary(result)
     with open(os.path.join(args.save, "Metrics.json"), "w") as fh:
@@ -432,7 +445,7 @@ def main_y4m(args):
         with open(args.timing_json, "w") as fh:
             json.dump(dict(per, frames=frames, seconds=t_end - t_first, fps=frames / (t_end - t_first), graph=args.graph, y4m=1,
                            hist_match=int(hm_on), lpips=int(lp_on), planes=int(plane_fmt is not None), **({"noref": 1} if noref else {}),
-                           **({"color": 1} if args.color else {}),
+                           **({"color": 1} if args.color else {}), **({"niqe": 1} if args.niqe else {}),
                            scene_wait_ms=1e3 * det.wait / frames if det is not None else None,
                            **({"tc": int(tc is not None), "tc_scale": args.tc_scale} if args.tc else {})), fh)
     logging.info("Total frame number: %d", frames)
@@ -464,6 +477,8 @@ def main():
     lpips_model = utils.lpips_model(args.lpips_weights, dev, args.lpips_precision) if args.lpips_weights else None
     total_lpips, total_lpips_hm = 0.0, 0.0
     color_means, color_blocks = {"out": grading.ColorMeans(), "gt": grading.ColorMeans()}, None
+    niqe_model = grading.NiqeModel.load(args.niqe) if args.niqe else None
+    niqe_tot, niqe_count, niqe_blocks = {"out": 0.0, "gt": 0.0}, {"out": 0, "gt": 0}, None
     step = None
     if args.graph:
         import importlib
@@ -512,6 +527,13 @@ def main():
                     v = utils.color_quality(frame, args.color_block)
                     color_means[which].add(v)
                     logging.info("NUM: %d, color %s: %s", n, which, grading.color_text(v))
+            if niqe_model is not None:                             # read back per image, as PSNR is
+                niqe_blocks = [output.shape[2] // 96, output.shape[3] // 96]
+                for which, frame in (("out", output), ("gt", gt_t)):
+                    v = utils.niqe(frame, niqe_model)
+                    if v is not None:
+                        niqe_tot[which], niqe_count[which] = niqe_tot[which] + v, niqe_count[which] + 1
+                    logging.info("NUM: %d, NIQE %s: %s", n, which, "null" if v is None else "%.4f" % v)
             if i < args.save_images:
                 parts = img_path[0].split(os.sep)
                 save_dir = os.path.join(args.save, parts[-3] + "/" + parts[-2])
@@ -540,6 +562,12 @@ def main():
                                "in": None, "gt": color_means["gt"].means()}
             logging.info("colour (%d images, blocks of %d): out %s; gt %s", n, args.color_block,
                          grading.color_text(result["color"]["out"]), grading.color_text(result["color"]["gt"]))
+        if niqe_model is not None:
+            means = {w: niqe_tot[w] / niqe_count[w] if niqe_count[w] else None for w in ("out", "gt")}
+            result["niqe"] = {"model": niqe_model.name, "blocks": niqe_blocks, "graded": "denoise", "out": means["out"], "in": None,
+                              "gt": means["gt"], "frames_with_value": niqe_count}
+            logging.info("NIQE (%d images, model %s): %s", n, niqe_model.name, ", ".join(
+                "%s: %s" % (w, "null" if result["niqe"][w] is None else "%.4f" % result["niqe"][w]) for w in ("out", "gt")))
         json.dump(result, fh)
 
 

@@ -517,6 +517,47 @@ int zt_color_ws_bytes(int H, int W, int block, size_t* bytes);
 int zt_color_stats_f32(const float* x, int H, int W, int block, const unsigned int* lin16, const float* flut, int max_workgroups,
                        void* ws, size_t ws_bytes, long long* out_i /* [18] */, double* out_f /* [7] */, zt_stream_t stream);
 
+/* ---- NIQE of a frame (zt_niqe.hip): evals.py --niqe MODEL, DESIGN 8n --------------------------------------------------------------
+ * Mittal, Soundararajan and Bovik 2013, as the MATLAB release's computefeature / computequality and its Python ports state it.
+ * Per-pixel work in unsigned integers or in fp32 with one rounding an operation, sums in fp64.
+ * x: planar fp32 [3][H][W].  Levels R, G, B = zt_quant_u8(v, 1); grey g = (19591 R + 38472 G + 7473 B + 32768) >> 16, 0..255.
+ * Crop: Hc = H / 96 * 96, Wc = W / 96 * 96 from the top left; everything below is about the cropped image.  k2 = Hc / 96,
+ * k1 = Wc / 96, nblk = k1 * k2, block b = i k1 + j is rows 96 i .., columns 96 j .. .
+ * Scale 1: x = (float)g, block side P = 96.  Scale 2: the half-size image (Hc / 2 x Wc / 2, P = 48) of MATLAB's imresize(., 0.5):
+ *   S[i][j] = sum_a sum_b t[a] t[b] g[rf(2i - 3 + a)][rf(2j - 3 + b)], t = (-3, -9, 29, 111, 111, 29, -9, -3), a, b = 0..7, in
+ *   integers (|S| < 2^25); rf reflects with the edge repeated (-1 -> 0, -2 -> 1, n -> n - 1); x2 = (float)S * (1.0f / 65536).
+ * MSCN field of either scale over its whole image: win = fp32 [7], the normalised Gaussian of sigma 7 / 6 rounded from fp64 by the
+ *   caller; rows then columns, indices clamped to the image; acc = win[0] p[0], then acc = acc + win[k] p[k], k = 1..6; mu from x, m2
+ *   from x * x (the product rounded once); sigma = sqrtf(fabsf(m2 - mu * mu)); m = (x - mu) / (sigma + 1.0f).  A sample of the
+ *   half-size image beyond its edge is the clamped sample of x2 (clamp first, then that sample's eight taps).
+ * Per block and scale five fields: f = 0: m; f = 1..4: m[y][x] * m[(y - dy) mod P][(x - dx) mod P], (dy, dx) = (0, 1), (1, 0), (1, 1),
+ *   (1, -1), the shift circular within the block.  Of field f: n_neg / n_pos = the samples v < 0 / v > 0, S2_neg / S2_pos = the sums of
+ *   v * v (rounded to fp32) over them, S_abs = the sum of |v|; S_sigma = the sum of sigma over the block (scale 1; 0 at scale 2).
+ * zt_niqe_block_sums_f32: out_i = int64 [2][nblk][10] = { n_neg, n_pos } of f = 0..4; out_f = fp64 [2][nblk][16] = { S2_neg, S2_pos,
+ *   S_abs } of f = 0..4, then S_sigma; scale 1 first.  One pass over x writes the grey levels of the cropped image into ws; then a
+ *   workgroup per tile (one block of one scale, at most max_workgroups of them, 0: no cap).  The order of every sum follows from P
+ *   alone: the same frame gives the same bits whatever max_workgroups is.  ws: 4-byte aligned, at least what zt_niqe_ws_bytes
+ *   reports (a pure host query); nothing in it is kept between calls.
+ * zt_niqe_frame_f32: sums_i / sums_f as above; r_gam, c1, c2: fp64 [9801] made by the caller over alpha_i = 0.2 + 0.001 i:
+ *   r_gam = Gamma(2/a)^2 / (Gamma(1/a) Gamma(3/a)) (strictly increasing), c1 = sqrt(Gamma(1/a) / Gamma(3/a)), c2 = Gamma(2/a) / Gamma(1/a).
+ *   The fit of a field, n = P * P, in fp64: l = sqrt(S2_neg / n_neg), r = sqrt(S2_pos / n_pos), gh = l / r,
+ *   rhat = (S_abs / n)^2 / ((S2_neg + S2_pos) / n), rn = rhat (gh^3 + 1)(gh + 1) / (gh^2 + 1)^2, pos = the first index that minimises
+ *   (r_gam[i] - rn)^2 (by bisection and a comparison of the two neighbours), alpha = 0.2 + 0.001 pos, bl = l c1[pos], br = r c1[pos],
+ *   mean = (br - bl) c2[pos].  n_neg = 0, n_pos = 0 or an rn that is not finite: every number of the fit is NaN.
+ *   Features of a scale: (alpha, (bl + br) / 2) of f = 0, then (alpha, mean, bl, br) of f = 1..4: 18; a block's row is scale 1 then
+ *   scale 2: 36.  A row is valid when all 36 are finite.
+ *   out_i = int64 [38] = { nblk, nv = the valid rows, count[36] = the finite values of each column };
+ *   out_f = fp64 [738] = { the sum of the finite values of each column [36], the mean of the valid rows [36], the scatter of the valid
+ *   rows about that mean, sum (f_i - mean_i)(f_j - mean_j), upper triangle row-major [666] }; mean and scatter are 0 when nv = 0.
+ *   One workgroup, rows in block order.  Deterministic.
+ * H or W < 96, H * W >= 2^31, nblk < 1, max_workgroups < 0, a NULL or misaligned pointer, a workspace too small: ZT_EINVAL.
+ * Nothing synchronises. */
+int zt_niqe_ws_bytes(int H, int W, size_t* bytes);
+int zt_niqe_block_sums_f32(const float* x, int H, int W, const float* win, int max_workgroups, void* ws, size_t ws_bytes,
+                           long long* out_i, double* out_f, zt_stream_t stream);
+int zt_niqe_frame_f32(const long long* sums_i, const double* sums_f, int nblk, const double* r_gam, const double* c1, const double* c2,
+                      long long* out_i /* [38] */, double* out_f /* [738] */, zt_stream_t stream);
+
 /* ---- result PNGs encoded on the device (zt_png.hip) ------------------------------------------------------------------
  * predict.py:57-61, 101-104 (and evals.py's --save_images files): `Image.fromarray(u8).save(path, "PNG")`.  src: uint8 [H][W][3] (what
  * zt_quantize_u8_hwc writes) -> out: a complete zlib stream (78 01, deflate blocks, big-endian Adler-32) of the Paeth-filtered

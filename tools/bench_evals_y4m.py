@@ -34,6 +34,14 @@
     blocks of 10, 8 and 64, next to `Ops.ssim_u8_dev` in the same process.  `--settings evals_noref evals_color --skip-kernels
     --skip-temporal --frames 128 --out profiles/color_1080p.json` is the run behind that file.
 
+(g) NIQE: `evals_niqe` = `evals_noref` with --niqe MODEL in part (b); the model is fitted first by tools/niqe_fit.py
+    from every 16th frame of the ground-truth clip.  And the two kernels alone at 1080p on three inputs (the low-light frame, its
+    clean twin, uniform noise): `Ops.niqe_block_sums`, `Ops.niqe_frame_from_sums`, both as `Ops.niqe_frame`, next to a plain-torch
+    composition of the same definition on the device (index gather and `F.conv2d` for the half-size image, `F.pad` / `F.conv2d` for
+    the window, `torch.roll` for the products, the fits by `torch.searchsorted`, `torch.cov`) and to `Ops.ssim_u8_dev`.
+    `--settings evals_noref evals_niqe --skip-kernels --skip-temporal --frames 128 --out profiles/niqe_1080p.json` is the run
+    behind that file.
+
 This driver never opens the GPU itself: every GPU step is a child process under its own `timeout -k 10`, and the first failure
 ends the run.  Writes the JSON to --out and prints it as one line.
 Usage: python tools/bench_evals_y4m.py [--frames 256] [--out profiles/evals_y4m_1080p.json]"""
@@ -278,6 +286,118 @@ def color_mode(a):
         json.dump(out, fh)
 
 
+# ---- child: the two kernels of zt_niqe.hip alone, next to a plain-torch composition of the same definition -----------------
+def torch_niqe(x, win, r_gam, c1, c2):
+    """the definition of include/zerotig_hip.h in plain torch on the device -> (column sums over finite, counts, nv, mean of the
+    valid rows, their covariance); float32 per pixel, float64 sums, as the kernels"""
+    import torch
+    import torch.nn.functional as F
+    Hc, Wc = x.shape[2] // 96 * 96, x.shape[3] // 96 * 96
+    lv = torch.round(x[0] * 255.0).to(torch.int64) & 255
+    g = ((19591 * lv[0] + 38472 * lv[1] + 7473 * lv[2] + 32768) >> 16)[:Hc, :Wc].to(torch.float32)
+
+    def sym(n):                                     # indices -3 .. n + 3, reflected with the edge repeated
+        i = torch.arange(-3, n + 4, device=x.device)
+        i = torch.where(i < 0, -i - 1, i)
+        return torch.where(i >= n, 2 * n - 1 - i, i)
+    t = torch.tensor([-3.0, -9.0, 29.0, 111.0, 111.0, 29.0, -9.0, -3.0], device=x.device) / 256.0
+    x2 = F.conv2d(g[sym(Hc)][:, sym(Wc)][None, None], torch.outer(t, t)[None, None], stride=2)[0, 0]
+    feats = []
+    for img, P in ((g, 96), (x2, 48)):
+        def filt(a):
+            a = F.conv2d(F.pad(a[None, None], (3, 3, 0, 0), mode="replicate"), win.view(1, 1, 1, 7))
+            return F.conv2d(F.pad(a, (0, 0, 3, 3), mode="replicate"), win.view(1, 1, 7, 1))[0, 0]
+        mu, m2 = filt(img), filt(img * img)
+        m = (img - mu) / (torch.sqrt(torch.abs(m2 - mu * mu)) + 1.0)
+        k2, k1 = m.shape[0] // P, m.shape[1] // P
+        mb = m.view(k2, P, k1, P).permute(0, 2, 1, 3).reshape(k2 * k1, P, P)
+        cols = []
+        for f, shift in enumerate((None, (0, 1), (1, 0), (1, 1), (1, -1))):
+            v = mb if shift is None else mb * torch.roll(mb, shift, dims=(1, 2))
+            sq, neg, pos = (v * v).double(), v < 0, v > 0
+            n_neg, n_pos = neg.sum(dim=(1, 2)), pos.sum(dim=(1, 2))
+            s2n, s2p = (sq * neg).sum(dim=(1, 2)), (sq * pos).sum(dim=(1, 2))
+            l, r = torch.sqrt(s2n / n_neg), torch.sqrt(s2p / n_pos)
+            gh = l / r
+            rhat = (v.abs().double().sum(dim=(1, 2)) / (P * P)) ** 2 / ((s2n + s2p) / (P * P))
+            rn = rhat * (gh ** 3 + 1.0) * (gh + 1.0) / (gh * gh + 1.0) ** 2
+            ok = (n_neg > 0) & (n_pos > 0) & torch.isfinite(rn)
+            j = torch.searchsorted(r_gam, torch.where(ok, rn, torch.ones_like(rn)))
+            lo, hi = (j - 1).clamp(0, 9800), j.clamp(0, 9800)
+            p = torch.where((r_gam[lo] - rn) ** 2 <= (r_gam[hi] - rn) ** 2, lo, hi)
+            nan = torch.full_like(rn, float("nan"))
+            alpha, bl, br = torch.where(ok, 0.2 + 0.001 * p, nan), torch.where(ok, l * c1[p], nan), torch.where(ok, r * c1[p], nan)
+            cols += [alpha, (bl + br) / 2.0] if f == 0 else [alpha, (br - bl) * c2[p], bl, br]
+        feats.append(torch.stack(cols, dim=1))
+    feat = torch.cat(feats, dim=1)
+    fin = torch.isfinite(feat)
+    valid = fin.all(dim=1)
+    rows = feat[valid]
+    return torch.where(fin, feat, torch.zeros_like(feat)).sum(dim=0), fin.sum(dim=0), valid.sum(), rows.mean(dim=0), torch.cov(rows.T)
+
+
+def niqe_mode(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("zero-tig_amd.lib").get_lib()               # raises without a HIP device
+    ops = importlib.import_module("zero-tig_amd.ops").Ops(lib)
+    synth = importlib.import_module("zero-tig_amd.synth")
+    grading = importlib.import_module("zero-tig_amd.grading")
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+
+    def dev_frame(x):
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(1, 3, H, W))).to(dev)
+
+    def timed(fn):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return {"ms": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
+    inputs = {"synth_lowlight": dev_frame(synth.lowlight_frame(3, H, W)), "synth_clean": dev_frame(synth.clean_frame(3, H, W)),
+              "uniform_noise": dev_frame(rng.random((3, H, W), dtype=np.float32))}
+    tabs = [torch.from_numpy(t).to(dev) for t in grading.niqe_tables()]
+    out = {"what": "HIP-event median of %d calls at 1080 x 1920 (220 blocks, 440 tiles): block_sums = Ops.niqe_block_sums (the grey pass "
+                   "over the frame, bytes = 12 H W, and the tile pass), block_sums_wgN = the same with max_workgroups = N, frame = "
+                   "Ops.niqe_frame_from_sums (one workgroup), niqe = Ops.niqe_frame (all three kernels), torch = the plain-torch "
+                   "composition of the same definition on the same device (tools/bench_evals_y4m.py torch_niqe), ssim_u8 = "
+                   "Ops.ssim_u8_dev of the frame against the clean frame, in the same process; max_feature_gap = the largest "
+                   "difference between the column means of the kernels and of the torch composition" % a.reps}
+    for name, x in inputs.items():
+        oi, of = torch.empty(38, dtype=torch.int64, device=dev), torch.empty(738, dtype=torch.float64, device=dev)
+        one = torch.empty(1, dtype=torch.float64, device=dev)
+        si, sf = ops.niqe_block_sums(x)
+        row = {"block_sums": timed(lambda: ops.niqe_block_sums(x, out_i=si, out_f=sf))}
+        row["block_sums"].update(bytes=12 * H * W, gbs=round(12 * H * W / row["block_sums"]["ms"] / 1e6, 1))
+        for wg in (110, 220, 256):
+            row["block_sums_wg%d" % wg] = timed(lambda: ops.niqe_block_sums(x, wg, out_i=si, out_f=sf))
+        row["frame"] = timed(lambda: ops.niqe_frame_from_sums(si, sf, out_i=oi, out_f=of))
+        row["niqe"] = timed(lambda: ops.niqe_frame(x, out_i=oi, out_f=of))
+        row["torch"] = timed(lambda: torch_niqe(x, *tabs))
+        row["ssim_u8"] = timed(lambda: ops.ssim_u8_dev(x, inputs["synth_clean"], out=one))
+        row["torch_over_niqe"] = round(row["torch"]["ms"] / row["niqe"]["ms"], 1)
+        ops.niqe_frame(x, out_i=oi, out_f=of)
+        colsum, count, nv, _, _ = torch_niqe(x, *tabs)
+        ints, floats = oi.tolist(), of.tolist()
+        mine = np.asarray(floats[:36]) / np.maximum(np.asarray(ints[2:38]), 1)
+        theirs = (colsum / count.clamp(min=1)).cpu().numpy()
+        row.update(valid_blocks=ints[1], torch_valid_blocks=int(nv.item()), max_feature_gap=float(np.abs(mine - theirs).max()),
+                   column_means=mine.tolist())
+        out[name] = row
+        print("[bench_evals_y4m] niqe %s %s" % (name, {k: v for k, v in row.items() if k != "column_means"}), file=sys.stderr, flush=True)
+    with open(a.json, "w") as fh:
+        json.dump(out, fh)
+
+
 # ---- child: the kernels of zt_flowviz.hip alone at the reduced size of --tc_scale 3 (DESIGN 8k) --------------------------------------
 def tcviz_mode(a):
     import numpy as np
@@ -392,7 +512,7 @@ def gpu_step(cmd, limit, env=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels", "temporal", "noref", "tcviz", "color"])
+    ap.add_argument("--mode", type=str, default="driver", choices=["driver", "kernels", "temporal", "noref", "tcviz", "color", "niqe"])
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--frames", type=int, default=256)
@@ -400,7 +520,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--settings", type=str, nargs="*", default=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1"],
                     choices=["predict", "evals", "evals_hm", "evals_lpips", "evals_tc3", "evals_tc1", "evals_noref", "evals_tcviz_pic",
-                             "evals_tcviz", "evals_color"])
+                             "evals_tcviz", "evals_color", "evals_niqe"])
     ap.add_argument("--skip-kernels", action="store_true", help="part (b) only")
     ap.add_argument("--skip-temporal", action="store_true", help="without the temporal kernel's own timing (part (c))")
     ap.add_argument("--step-timeout", type=int, default=240)
@@ -416,6 +536,8 @@ def main():
         return tcviz_mode(a)
     if a.mode == "color":
         return color_mode(a)
+    if a.mode == "niqe":
+        return niqe_mode(a)
     out = {"what": "evals.py --y4m_in / --y4m_gt next to predict.py --y4m_in, --graph 1 --precision bf16, over one synthetic 1080p "
                    "C420mpeg2 pair of %d frames (%d distinct), %d runs per setting, the runs alternating, one session on one box; fps "
                    "and the host-side split per frame from each script's --timing_json (predict: first frame read to last stream "
@@ -427,7 +549,9 @@ def main():
                    "noref_kernels = the two entry points of zt_noref.hip alone; evals_tcviz / evals_tcviz_pic = evals_tc3 with --tc_viz and "
                    "--tc_flo_dir / with --tc_viz alone (DESIGN 8k), tcviz_kernels = the kernels of zt_flowviz.hip alone; evals_color = "
                    "--noref 1 --color 1 (DESIGN 8m), the yardstick is evals_noref in the same run, color_kernels = zt_color_stats_f32 "
-                   "alone" % (a.frames, a.distinct, a.repeats, a.reps),
+                   "alone; evals_niqe = --noref 1 --niqe MODEL (DESIGN 8n), the model fitted by tools/niqe_fit.py from every 16th frame "
+                   "of the ground-truth clip, the yardstick is evals_noref in the same run, niqe_kernels = the kernels of zt_niqe.hip "
+                   "alone next to a plain-torch composition" % (a.frames, a.distinct, a.repeats, a.reps),
             "cpus": len(os.sched_getaffinity(0))}
     tmp = tempfile.mkdtemp(prefix="zt_bench_evals_y4m_")
     try:
@@ -451,6 +575,10 @@ def main():
             kj = os.path.join(tmp, "color.json")
             gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "color", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
             out["color_kernels"] = json.load(open(kj))
+        if "evals_niqe" in a.settings:
+            kj = os.path.join(tmp, "niqe.json")
+            gpu_step([sys.executable, os.path.abspath(__file__), "--mode", "niqe", "--json", kj, "--reps", str(a.reps)], a.step_timeout)
+            out["niqe_kernels"] = json.load(open(kj))
         files = make_pair(tmp, a.frames, a.distinct)
         viz, flo = os.path.join(tmp, "viz.y4m"), os.path.join(tmp, "flo")
         env = dict(os.environ, PYTHONPATH=ROOT)
@@ -461,6 +589,11 @@ def main():
                  "evals_tc1": ["--y4m_gt", files["gt"], "--hist_match", "0", "--tc", "1", "--tc_scale", "1"],
                  "evals_noref": ["--noref", "1"]}
         extra["evals_color"] = extra["evals_noref"] + ["--color", "1"]
+        if "evals_niqe" in a.settings:
+            files["niqe"] = os.path.join(tmp, "niqe_model.npz")
+            gpu_step([sys.executable, os.path.join(ROOT, "tools", "niqe_fit.py"), "--y4m", files["gt"], "--step", "16", "--out", files["niqe"]],
+                     a.step_timeout, env=dict(os.environ, PYTHONPATH=ROOT))
+            extra["evals_niqe"] = extra["evals_noref"] + ["--niqe", files["niqe"]]
         extra["evals_tcviz_pic"] = extra["evals_tc3"] + ["--tc_viz", viz]
         extra["evals_tcviz"] = extra["evals_tcviz_pic"] + ["--tc_flo_dir", flo]
         loops, wall, written = {s: [] for s in a.settings}, {s: [] for s in a.settings}, {}
@@ -502,6 +635,10 @@ def main():
             e2e = out["end_to_end"]
             e2e["evals_color"]["color_over_noref_ms_per_frame"] = round(e2e["evals_color"]["ms_per_frame_median"] -
                                                                         e2e["evals_noref"]["ms_per_frame_median"], 3)
+        if "evals_noref" in a.settings and "evals_niqe" in a.settings:
+            e2e = out["end_to_end"]
+            e2e["evals_niqe"]["niqe_over_noref_ms_per_frame"] = round(e2e["evals_niqe"]["ms_per_frame_median"] -
+                                                                      e2e["evals_noref"]["ms_per_frame_median"], 3)
         if "predict" in a.settings:
             base = out["end_to_end"]["predict"]["ms_per_frame_median"]
             for s in a.settings:

@@ -170,6 +170,20 @@ def color_quality(img, block=10):
     return grading.color_values(oi.tolist(), of.tolist(), block)
 
 
+def niqe(img, model):
+    """NIQE of a [1,3,H,W] frame in [0,1] on the device against `model` (a `grading.NiqeModel`, or the path of one)
+    -> float, or None where it has no value (fewer than two whole 96 x 96 blocks, or fewer than two blocks whose 36 features are
+    all finite); synchronous: 38 integers and 738 sums are read back."""
+    grading = importlib.import_module("zero-tig_amd.grading")
+    if not isinstance(model, grading.NiqeModel):
+        model = grading.NiqeModel.load(model)
+    x = _prep(img)
+    if (int(x.shape[2]) // 96) * (int(x.shape[3]) // 96) < 2:
+        return None
+    oi, of = _ops().niqe_frame(x)
+    return grading.niqe_value(oi.tolist(), of.tolist(), model)
+
+
 def lpips_model(path, device, precision="fp32"):
     """evals.py:73-80 `lpips.LPIPS(net='vgg')` on the device from the user's weights file (`torch.save(lpips.LPIPS(net='vgg')
     .state_dict(), path)`; torchvision's `features.<idx>.*` names are accepted for the convs).  precision: "fp32" or "bf16"."""

@@ -368,6 +368,180 @@ class ColorGrader:
                      "; ".join("%s %s" % (w, color_text(co[w])) for w in self.which))
 
 
+_NIQE_TABLES = []
+
+
+def niqe_tables():
+    """-> (win float32 [7], r_gam, c1, c2 float64 [9801]) as include/zerotig_hip.h defines them, made in float64; made once"""
+    import numpy as np
+    if not _NIQE_TABLES:
+        k = np.arange(-3, 4, dtype=np.float64)
+        win = np.exp(-k * k / (2.0 * (7.0 / 6.0) ** 2))
+        lg = math.lgamma
+        alpha = [0.2 + 0.001 * i for i in range(9801)]
+        r_gam = np.array([math.exp(2.0 * lg(2.0 / a) - lg(1.0 / a) - lg(3.0 / a)) for a in alpha], dtype=np.float64)
+        c1 = np.array([math.sqrt(math.exp(lg(1.0 / a) - lg(3.0 / a))) for a in alpha], dtype=np.float64)
+        c2 = np.array([math.exp(lg(2.0 / a) - lg(1.0 / a)) for a in alpha], dtype=np.float64)
+        assert bool(np.all(np.diff(r_gam) > 0))
+        _NIQE_TABLES.extend([(win / win.sum()).astype(np.float32), r_gam, c1, c2])
+    return tuple(_NIQE_TABLES)
+
+
+def niqe_features(sums_i, sums_f):
+    """the fits of the header in numpy float64, for the fitting of a model: what `Ops.niqe_block_sums` returns, read back
+    ([2,n,10], [2,n,16]) -> float64 [n,36], NaN where a fit has no value"""
+    import numpy as np
+    _, r_gam, c1, c2 = niqe_tables()
+    si, sf = np.asarray(sums_i, dtype=np.int64), np.asarray(sums_f, dtype=np.float64)
+    n = si.shape[1]
+    si, sf = si.reshape(2, n, 5, 2), sf[:, :, :15].reshape(2, n, 5, 3)
+    px = np.array([9216.0, 2304.0]).reshape(2, 1, 1)
+    with np.errstate(all="ignore"):
+        l, r = np.sqrt(sf[..., 0] / si[..., 0]), np.sqrt(sf[..., 1] / si[..., 1])
+        gh = l / r
+        rhat = (sf[..., 2] / px) ** 2 / ((sf[..., 0] + sf[..., 1]) / px)
+        rn = rhat * (gh * gh * gh + 1.0) * (gh + 1.0) / ((gh * gh + 1.0) * (gh * gh + 1.0))
+        ok = (si[..., 0] > 0) & (si[..., 1] > 0) & np.isfinite(rn)
+        j = np.searchsorted(r_gam, np.where(ok, rn, 1.0), side="left")
+        lo, hi = np.clip(j - 1, 0, 9800), np.clip(j, 0, 9800)
+        pos = np.where((r_gam[lo] - rn) ** 2 <= (r_gam[hi] - rn) ** 2, lo, hi)
+        alpha = np.where(ok, 0.2 + 0.001 * pos, np.nan)
+        bl, br = np.where(ok, l * c1[pos], np.nan), np.where(ok, r * c1[pos], np.nan)
+        mean = (br - bl) * c2[pos]
+    feat = np.empty((n, 36), dtype=np.float64)
+    for s in range(2):
+        feat[:, 18 * s], feat[:, 18 * s + 1] = alpha[s, :, 0], (bl[s, :, 0] + br[s, :, 0]) / 2.0
+        for f in range(1, 5):
+            feat[:, 18 * s + 4 * f - 2:18 * s + 4 * f + 2] = np.stack([alpha[s, :, f], mean[s, :, f], bl[s, :, f], br[s, :, f]], axis=1)
+    return feat
+
+
+def _triu_to_full(tri, n=36):
+    import numpy as np
+    full = np.zeros((n, n), dtype=np.float64)
+    full[np.triu_indices(n)] = np.asarray(tri, dtype=np.float64)
+    return full + np.triu(full, 1).T
+
+
+def niqe_value(ints, floats, model):
+    """NIQE of a frame from what `Ops.niqe_frame` returns, 38 integers and 738 floats as include/zerotig_hip.h lists
+    them, against the pristine `model`; float64 on the host; None when fewer than two rows are valid or a column has no finite value"""
+    import numpy as np
+    nv, count = ints[1], np.asarray(ints[2:38], dtype=np.float64)
+    if nv < 2 or bool(np.any(count == 0)):
+        return None
+    mu_d = np.asarray(floats[0:36], dtype=np.float64) / count
+    cov_d = _triu_to_full(floats[72:738]) / (nv - 1)
+    d = model.mu - mu_d
+    q = float(d @ np.linalg.pinv((model.cov + cov_d) / 2.0) @ d)
+    return math.sqrt(max(q, 0.0)) if math.isfinite(q) else None
+
+
+class NiqeModel:
+    """the pristine model of NIQE: `mu` float64 [36], `cov` float64 [36,36]; `name` says where it came from"""
+
+    def __init__(self, mu, cov, name="model"):
+        import numpy as np
+        mu, cov = np.asarray(mu, dtype=np.float64), np.asarray(cov, dtype=np.float64)
+        assert mu.shape in ((36,), (1, 36)) and cov.shape == (36, 36), (mu.shape, cov.shape)
+        self.mu, self.cov, self.name = mu.reshape(36), cov, name
+
+    @classmethod
+    def load(cls, path):
+        """.npz with mu_pris_param / cov_pris_param (the Python ports' file, and `save`'s); .mat with mu_prisparam / cov_prisparam
+        (the MATLAB release's modelparameters.mat), which needs scipy"""
+        import numpy as np
+        if str(path).lower().endswith(".mat"):
+            try:
+                from scipy.io import loadmat
+            except ImportError:
+                raise ValueError("%s: reading a .mat model needs scipy, which cannot be imported here; convert it to .npz with the "
+                                 "keys mu_pris_param [36] and cov_pris_param [36,36]" % path)
+            data, keys = loadmat(path), ("mu_prisparam", "cov_prisparam")
+            found = sorted(k for k in data if not k.startswith("__"))
+        else:
+            data, keys = np.load(path), ("mu_pris_param", "cov_pris_param")
+            found = sorted(data.files)
+        if keys[0] not in found or keys[1] not in found:
+            raise ValueError("%s: a NIQE model holds %s and %s; the file holds %s" % (path, keys[0], keys[1], found))
+        mu, cov = np.asarray(data[keys[0]], dtype=np.float64), np.asarray(data[keys[1]], dtype=np.float64)
+        if mu.shape not in ((36,), (1, 36)) or cov.shape != (36, 36):
+            raise ValueError("%s: %s must be [36] or [1,36] and %s [36,36]; they are %s and %s (the file holds %s)"
+                             % (path, keys[0], keys[1], list(mu.shape), list(cov.shape), found))
+        return cls(mu, cov, os.path.basename(str(path)))
+
+    def save(self, path):
+        import numpy as np
+        with open(path, "wb") as fh:               # a file object: numpy adds no suffix of its own
+            np.savez(fh, mu_pris_param=self.mu.reshape(1, 36), cov_pris_param=self.cov)
+
+    @staticmethod
+    def select(sums_f):
+        """the blocks of one frame that go into a model (paper section 3): sharpness S_sigma / 9216 at scale 1 greater than 0.75
+        times the frame's largest -> bool [n]"""
+        import numpy as np
+        sharp = np.asarray(sums_f, dtype=np.float64)[0, :, 15] / 9216.0
+        return sharp > 0.75 * sharp.max()
+
+    @classmethod
+    def fit(cls, frames, name="fitted"):
+        """`frames`: per frame what `Ops.niqe_block_sums` returned, read back, (sums_i [2,n,10], sums_f [2,n,16]).  The sharp
+        blocks of every frame (`select`), their 36 features by `niqe_features`; mu = the mean of each column over its finite
+        values, cov = the sample covariance of the rows that are all finite about their own mean."""
+        import numpy as np
+        rows = [niqe_features(si, sf)[cls.select(sf)] for si, sf in frames]
+        feat = np.concatenate(rows, axis=0) if rows else np.zeros((0, 36))
+        valid = feat[np.all(np.isfinite(feat), axis=1)]
+        if valid.shape[0] < 2 or not bool(np.all(np.any(np.isfinite(feat), axis=0))):
+            raise ValueError("a NIQE model needs at least two sharp blocks whose features are all finite; got %d of %d"
+                             % (valid.shape[0], feat.shape[0]))
+        model = cls(np.nanmean(feat, axis=0), np.cov(valid, rowvar=False, ddof=1), name)
+        model.blocks = (int(valid.shape[0]), int(feat.shape[0]))
+        return model
+
+
+class NiqeGrader:
+    """--niqe MODEL: one `Ops.niqe_frame` per graded frame; `which` names the frames as `ColorGrader`'s does.  A frame
+    with fewer than two whole blocks is not graded: its cells stay zero, which `niqe_value` reads as no value."""
+
+    def __init__(self, tab, ops, model, which):
+        self.ops, self.model, self.which = ops, model, tuple(which)
+        self.cols = {w: (tab.ints("niqe_" + w, 38), tab.floats("niqe_" + w + "_sums", 738)) for w in self.which}
+        self.tot, self.count = dict.fromkeys(self.which, 0.0), dict.fromkeys(self.which, 0)
+        self.blocks = None                         # [k2, k1] of the frames, known from the first one
+
+    def launch(self, ctx, ri, rf):
+        frames = {"out": ctx.output, "in": ctx.step.x, "gt": ctx.gt}
+        if self.blocks is None:
+            self.blocks = [int(ctx.output.shape[2]) // 96, int(ctx.output.shape[3]) // 96]
+        if self.blocks[0] * self.blocks[1] < 2:
+            return
+        for w in self.which:
+            ci, cf = self.cols[w]
+            self.ops.niqe_frame(frames[w], out_i=ri[ci], out_f=rf[cf])
+
+    def read(self, n, rec, ri, rf):
+        rec["niqe"] = {"out": None, "in": None, "gt": None, "valid_blocks": {}}
+        for w in self.which:
+            ci, cf = self.cols[w]
+            v = niqe_value(ri[ci], rf[cf], self.model)
+            if v is not None:                      # the means count only the frames that have a value
+                self.tot[w] += v
+                self.count[w] += 1
+            rec["niqe"][w] = v
+            rec["niqe"]["valid_blocks"][w] = ri[ci][1]
+        logging.info("NUM: %d, NIQE %s", n, ", ".join("%s: %s" % (w, "null" if rec["niqe"][w] is None else "%.4f" % rec["niqe"][w])
+                                                       for w in self.which))
+
+    def summary(self, result):
+        nq = {"model": self.model.name, "blocks": self.blocks, "graded": "denoise", "out": None, "in": None, "gt": None,
+              "frames_with_value": dict(self.count)}
+        nq.update({w: self.tot[w] / self.count[w] if self.count[w] else None for w in self.which})
+        result["niqe"] = nq
+        logging.info("NIQE (%d frames, model %s): %s", result["images"], self.model.name,
+                     ", ".join("%s: %s" % (w, "null" if nq[w] is None else "%.4f" % nq[w]) for w in self.which))
+
+
 class NorefGrader:
     """--noref 1: `Ops.noref` of the decoded input as the network saw it (step.x) against the output, on the full
     grid and on the LOE_50 grid `grid50`"""

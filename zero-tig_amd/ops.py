@@ -719,6 +719,76 @@ class Ops:
                       c["ws"].numel() * 8, out_i, out_f, self._s(x))
         return out_i, out_f
 
+    # ---- NIQE of a frame (zt_niqe.hip) --------------------------------------------------------------------
+    def _niqe_cache(self, dev):
+        """the Gaussian window and the three Gamma tables, made here in float64, and the buffers, per device"""
+        from .grading import niqe_tables
+        cache = self.__dict__.setdefault("_niqe_caches", {})
+        c = cache.get(str(dev))
+        if c is None:
+            win, r_gam, c1, c2 = niqe_tables()
+            c = cache[str(dev)] = {"win": torch.from_numpy(win).to(dev), "r_gam": torch.from_numpy(r_gam).to(dev),
+                                   "c1": torch.from_numpy(c1).to(dev), "c2": torch.from_numpy(c2).to(dev), "ws": None, "sums": {}}
+        return c
+
+    def niqe_block_sums(self, x, max_workgroups=0, out_i=None, out_f=None):
+        """the block sums of NIQE of the fp32 [1,3,H,W] frame `x` (H, W >= 96), both scales -> (int64 [2,nblk,10], float64
+        [2,nblk,16]) on the device, as include/zerotig_hip.h lists them; nblk = (H // 96) * (W // 96).  Nothing synchronises.
+        `max_workgroups` caps the grid of the tile pass (0: no cap); the sums do not depend on it."""
+        import ctypes
+        _f32c(x)
+        assert x.dim() == 4 and x.shape[0] == 1 and x.shape[1] == 3, tuple(x.shape)
+        H, W = int(x.shape[2]), int(x.shape[3])
+        assert H >= 96 and W >= 96 and H * W < 1 << 31, (H, W)
+        assert int(max_workgroups) == max_workgroups and max_workgroups >= 0, max_workgroups
+        dev, nblk = x.device, (H // 96) * (W // 96)
+        c = self._niqe_cache(dev)
+        need = ctypes.c_size_t(0)
+        self.lib.call("zt_niqe_ws_bytes", H, W, ctypes.byref(need))
+        if c["ws"] is None or c["ws"].numel() * 8 < need.value:
+            c["ws"] = torch.empty((need.value + 7) // 8, dtype=torch.int64, device=dev)
+        if out_i is None:
+            out_i = torch.empty((2, nblk, 10), dtype=torch.int64, device=dev)
+        if out_f is None:
+            out_f = torch.empty((2, nblk, 16), dtype=torch.float64, device=dev)
+        assert tuple(out_i.shape) == (2, nblk, 10) and out_i.dtype == torch.int64 and out_i.is_contiguous() and out_i.device == dev
+        assert tuple(out_f.shape) == (2, nblk, 16) and out_f.dtype == torch.float64 and out_f.is_contiguous() and out_f.device == dev
+        self.lib.call("zt_niqe_block_sums_f32", x, H, W, c["win"], int(max_workgroups), c["ws"], c["ws"].numel() * 8, out_i, out_f,
+                      self._s(x))
+        return out_i, out_f
+
+    def niqe_frame_from_sums(self, sums_i, sums_f, out_i=None, out_f=None):
+        """the ten fits of every block and the frame's reduction from what `niqe_block_sums` returns (or the same of any rows of
+        it, [2,n,10] / [2,n,16]) -> (int64 [38], float64 [738]) on the device; `grading.niqe_value` turns them into the score"""
+        dev = sums_i.device
+        nblk = int(sums_i.shape[1])
+        assert nblk >= 1 and tuple(sums_i.shape) == (2, nblk, 10) and sums_i.dtype == torch.int64 and sums_i.is_contiguous()
+        assert tuple(sums_f.shape) == (2, nblk, 16) and sums_f.dtype == torch.float64 and sums_f.is_contiguous() and sums_f.device == dev
+        c = self._niqe_cache(dev)
+        if out_i is None:
+            out_i = torch.empty(38, dtype=torch.int64, device=dev)
+        if out_f is None:
+            out_f = torch.empty(738, dtype=torch.float64, device=dev)
+        assert tuple(out_i.shape) == (38,) and out_i.dtype == torch.int64 and out_i.is_contiguous() and out_i.device == dev
+        assert tuple(out_f.shape) == (738,) and out_f.dtype == torch.float64 and out_f.is_contiguous() and out_f.device == dev
+        self.lib.call("zt_niqe_frame_f32", sums_i, sums_f, nblk, c["r_gam"], c["c1"], c["c2"], out_i, out_f, self._s(sums_i))
+        return out_i, out_f
+
+    def niqe_frame(self, x, out_i=None, out_f=None):
+        """the raw numbers of NIQE of the fp32 [1,3,H,W] frame `x` (H, W >= 96) -> (int64 [38], float64 [738]) on the device:
+        {nblk, valid rows, count per column}, {column sums, mean of the valid rows, their centred scatter}.  Nothing synchronises;
+        `out_i` / `out_f` (e.g. cells of a table row) are overwritten.  The block sums between the two kernels, the tables and the
+        workspace are cached per device."""
+        H, W = int(x.shape[2]), int(x.shape[3])
+        nblk = (H // 96) * (W // 96)
+        assert nblk >= 1, (H, W)
+        c = self._niqe_cache(x.device)
+        if nblk not in c["sums"]:
+            c["sums"][nblk] = (torch.empty((2, nblk, 10), dtype=torch.int64, device=x.device),
+                               torch.empty((2, nblk, 16), dtype=torch.float64, device=x.device))
+        si, sf = self.niqe_block_sums(x, out_i=c["sums"][nblk][0], out_f=c["sums"][nblk][1])
+        return self.niqe_frame_from_sums(si, sf, out_i, out_f)
+
     def psnr_u8(self, a, b):
         """evals.py:83-85: cv2.PSNR of round(a*255), round(b*255) -> python float (inf when identical); one 8-byte read-back."""
         _f32c(a), _f32c(b)
