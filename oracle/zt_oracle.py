@@ -328,10 +328,87 @@ def _fma32(a, b, c):
     return (a.double() * b.double() + c.double()).float()
 
 
+def lin_index32(in_size, out_size):
+    """Source indices and weights of one axis of F.interpolate(bilinear, align_corners=False), as the kernels' `lin_index`
+    documents them (ATen compute_source_index_and_lambda with area_pixel_compute_scale<float>): everything in fp32,
+    src = fma(scale, dst + 0.5, -0.5) clamped at 0, i0 = floor(src), lambda = src - i0.  -> (i0, i1 int64, w0, w1 fp32)."""
+    dst = torch.arange(out_size)
+    if in_size == out_size:
+        return dst, dst.clone(), torch.ones(out_size), torch.zeros(out_size)
+    scale = torch.tensor(float(in_size), dtype=torch.float32) / torch.tensor(float(out_size), dtype=torch.float32)
+    src = _fma32(scale, dst.float() + 0.5, torch.tensor(-0.5)).clamp(min=0.0)
+    i0 = src.floor().long().clamp(max=in_size - 1)
+    lam = (src - i0.float()).clamp(0.0, 1.0)
+    return i0, i0 + (i0 < in_size - 1).long(), 1.0 - lam, lam
+
+
+def _bilinear_taps(x, h, w):
+    H, W = x.shape[-2:]
+    y0, y1, wy0, wy1 = lin_index32(H, h)
+    x0, x1, wx0, wx1 = lin_index32(W, w)
+    r0, r1 = x[..., y0, :], x[..., y1, :]
+    return (r0[..., x0], r0[..., x1], r1[..., x0], r1[..., x1]), (wx0, wx1, wy0[:, None], wy1[:, None])
+
+
+def bilinear_fma32(x, h, w, mul=None):
+    """F.interpolate(x, (h, w), mode="bilinear") [* mul] as the documented sequence of fp32 operations, at EVERY shape:
+    row = fma(a, w0, b * w1); out = fma(r0, wy0, r1 * wy1); the product with `mul` is one more fp32 rounding.  Equal sizes on
+    both axes copy.  (ATen's CPU kernel gives these bits at wide outputs only -- tests/test_raft_ends.py pins where.)"""
+    if tuple(x.shape[-2:]) == (h, w):
+        out = x.clone()
+    else:
+        (a, b, c, d), (wx0, wx1, wy0, wy1) = _bilinear_taps(x.float(), h, w)
+        out = _fma32(_fma32(a, wx0, b * wx1), wy0, _fma32(c, wx0, d * wx1) * wy1)
+    return out if mul is None else out * torch.tensor(mul, dtype=torch.float32)
+
+
+def bilinear_f64(x, h, w, mul=1.0):
+    """the definition bilinear_fma32 rounds: the same fp32-derived indices and weights, every product and sum in fp64"""
+    if tuple(x.shape[-2:]) == (h, w):
+        return x.double() * mul
+    (a, b, c, d), (wx0, wx1, wy0, wy1) = _bilinear_taps(x.double(), h, w)
+    wx0, wx1, wy0, wy1 = wx0.double(), wx1.double(), wy0.double(), wy1.double()
+    return ((a * wx0 + b * wx1) * wy0 + (c * wx0 + d * wx1) * wy1) * mul
+
+
+def warp_fma32(flow, img):
+    """warp_tensor(flow, img) as the documented sequence of fp32 operations (zt_warp.hip), exact at every shape:
+    coordinate maps (utils.py:215-216) up-sampled by bilinear_fma32, g = m / ((size - 1) / 2) - 1, ix = fma(g + 1, size / 2, -0.5),
+    x0 = floor(ix), wx1 = ix - x0, wx0 = 1 - wx1, w = wx * wy, v = nw * wnw; v = fma(ne, wne, v); v = fma(sw, wsw, v);
+    v = fma(se, wse, v) with a tap outside the image read as 0.  flow [1,2,Hf,Wf], img [1,C,H,W] ->
+    (out [1,C,H,W], (x0, y0) fp32 [H,W,2] before any integer conversion, inside [4,H,W] bool: nw, ne, sw, se in the image)."""
+    _, C, H, W = img.shape
+    Hf, Wf = flow.shape[-2:]
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    gy, gx = torch.meshgrid(torch.arange(Hf, dtype=torch.float32), torch.arange(Wf, dtype=torch.float32), indexing="ij")
+    mx = bilinear_fma32((gx - flow[0, 0]) * f32(float(H) / float(Hf)), H, W)       # sic: x by the height ratio
+    my = bilinear_fma32((gy - flow[0, 1]) * f32(float(W) / float(Wf)), H, W)
+    ix = _fma32(mx / f32((W - 1) / 2.0) - 1.0 + 1.0, f32(W) / 2.0, f32(-0.5))
+    iy = _fma32(my / f32((H - 1) / 2.0) - 1.0 + 1.0, f32(H) / 2.0, f32(-0.5))
+    fx0, fy0 = torch.floor(ix), torch.floor(iy)
+    wx1, wy1 = ix - fx0, iy - fy0
+    wx0, wy0 = 1.0 - wx1, 1.0 - wy1
+    # the kernels' fminf(fmaxf(v, -2), size + 1): a NaN becomes -2, far outside like every other coordinate that samples nothing
+    x0 = torch.where(torch.isnan(fx0), f32(-2.0), fx0.clamp(-2.0, W + 1.0)).long()
+    y0 = torch.where(torch.isnan(fy0), f32(-2.0), fy0.clamp(-2.0, H + 1.0)).long()
+    out = None
+    inside = []
+    for dy, dx, wgt in ((0, 0, wx0 * wy0), (0, 1, wx1 * wy0), (1, 0, wx0 * wy1), (1, 1, wx1 * wy1)):
+        xx, yy = x0 + dx, y0 + dy
+        ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+        t = torch.where(ok, img[0][:, yy.clamp(0, H - 1), xx.clamp(0, W - 1)], f32(0.0))
+        out = t * wgt if out is None else _fma32(t, wgt, out)
+        inside.append(ok)
+    return out[None], torch.stack([fx0, fy0], -1), torch.stack(inside)
+
+
 def warp_taps(flow, h_dst, w_dst):
     """Integer tap indices (x0, y0) of warp_tensor's grid_sample, with ATen's CPU arithmetic
     (GridSamplerKernel.cpp, align_corners=False): ix = fma(gx + 1, W/2, -0.5); x0 = floor(ix).
-    Established bit-for-bit against torch 2.10 CPU in the build container.  int32 [B,h_dst,w_dst,2]."""
+    The coordinate maps under it come from F.interpolate, whose bits are those of the documented fma sequence (bilinear_fma32)
+    at wide outputs only: seen equal at every width >= 128 and one ulp apart in about half the pixels at widths <= 72
+    (torch 2.10 CPU).  There the indices can differ wherever a coordinate sits within an ulp of an integer; warp_fma32 is
+    the reference that is exact at every shape.  int32 [B,h_dst,w_dst,2]."""
     grid = warp_coords(flow, h_dst, w_dst)
     half = torch.tensor(-0.5)
     ix = _fma32(grid[..., 0] + 1, torch.tensor(w_dst / 2.0, dtype=torch.float32), half)

@@ -26,6 +26,34 @@ __device__ __forceinline__ float zt_clampf(float v, float lo, float hi) {
   return fminf(fmaxf(v, lo), hi);
 }
 
+// One axis of F.interpolate(bilinear, align_corners=False): ATen compute_source_index_and_lambda (UpSample.h:451-476) with
+// scale = area_pixel_compute_scale<float> = (float)in_size / (float)out_size.  Used by the resize (zt_raft.hip) and by the warp's
+// coordinate up-sampling (zt_warp.hip); oracle.lin_index32 restates it and tests/test_raft_ends.py pins both users to it.
+struct ZtLin1 {
+  int i0, i1;
+  float w0, w1;
+};
+
+__device__ __forceinline__ ZtLin1 zt_lin_index(int dst, int in_size, int out_size, float scale) {
+  ZtLin1 r;
+  if (in_size == out_size) {
+    r.i0 = r.i1 = dst;
+    r.w0 = 1.f;
+    r.w1 = 0.f;
+    return r;
+  }
+  float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
+  src = src < 0.f ? 0.f : src;
+  int i0 = (int)floorf(src);
+  i0 = i0 < in_size - 1 ? i0 : in_size - 1;
+  float lam = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
+  r.i0 = i0;
+  r.i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+  r.w1 = lam;
+  r.w0 = 1.f - lam;
+  return r;
+}
+
 // float in [0, 1] -> 8-bit level, the two ways the reference scripts do it (zt_io.hip, zt_metrics.hip)
 __device__ __forceinline__ int zt_quant_u8(float v, int mode) {
   const float s = v * 255.f;

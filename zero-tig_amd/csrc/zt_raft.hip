@@ -6,37 +6,15 @@
 
 namespace {
 
-struct Lin1 {
-  int i0, i1;
-  float w0, w1;
-};
-
-__device__ __forceinline__ Lin1 lin_index(int dst, int in_size, int out_size, float scale) {
-  Lin1 r;
-  if (in_size == out_size) {
-    r.i0 = r.i1 = dst;
-    r.w0 = 1.f;
-    r.w1 = 0.f;
-    return r;
-  }
-  float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
-  src = src < 0.f ? 0.f : src;
-  int i0 = (int)floorf(src);
-  i0 = i0 < in_size - 1 ? i0 : in_size - 1;
-  float lam = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-  r.i0 = i0;
-  r.i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  r.w1 = lam;
-  r.w0 = 1.f - lam;
-  return r;
-}
-
-// F.interpolate(bilinear, align_corners=False) * mul  (model.py:226-227, 231) -- ATen CPU arithmetic
+// F.interpolate(bilinear, align_corners=False) * mul  (model.py:226-227, 231) as one fixed sequence of fp32 operations:
+// zt_lin_index on each axis, row = fma(a, w0, b * w1), out = fma(r0, wy0, r1 * wy1), then one product with mul.  Bit for bit
+// oracle.bilinear_fma32 at every shape; ATen's CPU kernel gives the same bits at the output widths the path runs (seen equal
+// from 128 up, one ulp apart in about half the pixels at 72 and below: tests/test_raft_ends.py).
 __global__ void __launch_bounds__(256) resize_bilinear_kernel(const float* __restrict__ src, float* __restrict__ dst, int C,
                                                               int H, int W, int h, int w, float sc_h, float sc_w, float mul) {
   int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
   if (x >= w || y >= h) return;
-  Lin1 ly = lin_index(y, H, h, sc_h), lx = lin_index(x, W, w, sc_w);
+  ZtLin1 ly = zt_lin_index(y, H, h, sc_h), lx = zt_lin_index(x, W, w, sc_w);
   for (int c = 0; c < C; ++c) {
     const float* p = src + (size_t)c * H * W;
     float a = p[(size_t)ly.i0 * W + lx.i0], b = p[(size_t)ly.i0 * W + lx.i1];

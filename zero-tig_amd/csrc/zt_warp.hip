@@ -2,39 +2,15 @@
 // flow at model.py:249-250) fused into ONE pass: coordinate-map construction, bilinear up-sampling of the maps,
 // grid normalisation and grid_sample(bilinear, zeros, align_corners=False) for both cached tensors.
 //
-// Integer contract: the tap indices floor(ix), floor(iy) reproduce ATen's CPU arithmetic bit for bit
-// (fma source index, fma row interpolation, ix = fma(g+1, W/2, -0.5)); this file is compiled with
-// -ffp-contract=off so only the explicit fmaf() calls fuse.
+// Integer contract: the tap indices floor(ix), floor(iy) and the warped values follow one fixed sequence of fp32 operations
+// (fma source index, fma row interpolation, ix = fma(g+1, W/2, -0.5), fma tap accumulation), restated as oracle.warp_fma32 and
+// equal to it bit for bit at every shape; this file is compiled with -ffp-contract=off so only the explicit fmaf() calls fuse.
+// It is the sequence of ATen's CPU kernels at the image widths the path runs: oracle.warp_tensor / warp_taps give the same bits
+// for images 128 wide and more, and differ in the last place of the up-sampled coordinates at 72 and below, where ATen
+// interpolates with another arithmetic (tests/test_raft_ends.py).
 #include "zt_common.h"
 
 namespace {
-
-struct Lin1 {
-  int i0, i1;
-  float w0, w1;
-};
-
-// ATen compute_source_index_and_lambda (UpSample.h:451-476), align_corners=False
-__device__ __forceinline__ Lin1 lin_index(int dst, int in_size, int out_size, float scale) {
-  Lin1 r;
-  if (in_size == out_size) {
-    r.i0 = r.i1 = dst;
-    r.w0 = 1.f;
-    r.w1 = 0.f;
-    return r;
-  }
-  float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
-  src = src < 0.f ? 0.f : src;
-  int i0 = (int)floorf(src);
-  i0 = i0 < in_size - 1 ? i0 : in_size - 1;
-  float lam = src - (float)i0;
-  lam = fminf(fmaxf(lam, 0.f), 1.f);
-  r.i0 = i0;
-  r.i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  r.w1 = lam;
-  r.w0 = 1.f - lam;
-  return r;
-}
 
 __device__ __forceinline__ float tap(const float* __restrict__ img, int x, int y, int W, int H) {
   return (x >= 0 && x < W && y >= 0 && y < H) ? img[(size_t)y * W + x] : 0.f;
@@ -49,8 +25,8 @@ __global__ void __launch_bounds__(256) warp2_kernel(const float* __restrict__ fl
   int x = blockIdx.x * 64 + threadIdx.x;
   int y = blockIdx.y * 4 + threadIdx.y;
   if (x >= W || y >= H) return;
-  Lin1 ly = lin_index(y, Hf, H, sc_h);
-  Lin1 lx = lin_index(x, Wf, W, sc_w);
+  ZtLin1 ly = zt_lin_index(y, Hf, H, sc_h);
+  ZtLin1 lx = zt_lin_index(x, Wf, W, sc_w);
   const float* fx = flow;
   const float* fy = flow + (size_t)Hf * Wf;
   // coordinate maps at flow resolution (utils.py:215-216; x scaled by h_scale, y by w_scale -- sic)
@@ -129,10 +105,10 @@ __global__ void __launch_bounds__(256) warp2_tiled_kernel(const float* __restric
   __shared__ float fs[2 * fwin_h * fwin_w];                      // flow window [2][fwin_h][fwin_w] (flow resolution <= image resolution)
   const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 64 + tx;
   const int xb = blockIdx.x * 64, yb = blockIdx.y * (4 * PPT);
-  // flow window: source rows / columns touched by the tile's first and last pixel (lin_index is monotone in dst)
+  // flow window: source rows / columns touched by the tile's first and last pixel (zt_lin_index is monotone in dst)
   const int xe = min(xb + 63, W - 1), ye = min(yb + 4 * PPT - 1, H - 1);
-  const int fx0 = lin_index(xb, Wf, W, sc_w).i0, fx1 = lin_index(xe, Wf, W, sc_w).i1;
-  const int fy0 = lin_index(yb, Hf, H, sc_h).i0, fy1 = lin_index(ye, Hf, H, sc_h).i1;
+  const int fx0 = zt_lin_index(xb, Wf, W, sc_w).i0, fx1 = zt_lin_index(xe, Wf, W, sc_w).i1;
+  const int fy0 = zt_lin_index(yb, Hf, H, sc_h).i0, fy1 = zt_lin_index(ye, Hf, H, sc_h).i1;
   const int ww = fx1 - fx0 + 1, wh = fy1 - fy0 + 1;
   const size_t fplane = (size_t)Hf * Wf;
   for (int e = tid; e < 2 * wh * ww; e += 256) {
@@ -145,11 +121,11 @@ __global__ void __launch_bounds__(256) warp2_tiled_kernel(const float* __restric
   const size_t plane = (size_t)H * W;
   int px0[PPT], py0[PPT];
   float wnw[PPT], wne[PPT], wsw[PPT], wse[PPT];
-  const Lin1 lx = lin_index(min(x, W - 1), Wf, W, sc_w);
+  const ZtLin1 lx = zt_lin_index(min(x, W - 1), Wf, W, sc_w);
 #pragma unroll
   for (int j = 0; j < PPT; ++j) {
     const int y = min(yb + ty + 4 * j, H - 1);
-    const Lin1 ly = lin_index(y, Hf, H, sc_h);
+    const ZtLin1 ly = zt_lin_index(y, Hf, H, sc_h);
     const float* fx = fs + ((ly.i0 - fy0) * fwin_w - fx0);
     const float* gx = fs + ((ly.i1 - fy0) * fwin_w - fx0);
     const float* fy = fx + fwin_h * fwin_w;

@@ -1074,7 +1074,8 @@ class Ops:
 
     def corr_volume_pyramid_bf16(self, fmap1, fmap2, h, w, alpha):
         """fmap1 / fmap2: bf16 [.., 256]-channel NHWC feature maps of the two frames ([npx][ld] views) -> (corr0 [1,h,w,ld0] fp32,
-        [level1, level2, level3]) in one launch (corr.py:13-27, 52-60)."""
+        [level1, level2, level3]) in one launch (corr.py:13-27, 52-60).  ld0 = npx rounded up to 4; the launch does not write the
+        padding columns npx .. ld0 - 1 of corr0, which keep whatever the allocation held (the lookup never reads them)."""
         npx = h * w
         ld0 = (npx + 3) // 4 * 4
         dev = fmap1.device
